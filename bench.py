@@ -9,8 +9,11 @@ would run; every step still does the whole path on its own batch); ``value_seria
 K steps on one stream. Multi-GPU: one process per GPU (torchrun), each rank owns its
 own images (weak scaling, no data-path collective); barrier + max-over-ranks timing.
 
-Prints ONE JSON line (rank 0). Extra fields: isolated-MPN edge-updates/s, live roofline of the
-dominant kernel (hipEvents on the launch stream), and the CPU oracle baseline (rank 0, N=1).
+Prints ONE JSON line (rank 0). A plain run does only what `value` needs: set-up, the schedule probe, the
+warm-up, the K timed steps, and with ``--dump-outputs DIR`` the last timed step's outputs as DIR/<name>.npy.
+``--full`` adds the legs beside it: the same steps serial, isolated-MPN edge-updates/s, live roofline of the
+dominant kernel (hipEvents on the launch stream), the e2e pipeline, the front-end and grouping legs, the
+backbone leg and the CPU oracle baseline (rank 0, N=1).
 """
 import argparse
 import ctypes
@@ -73,12 +76,21 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)   # (a 20-step region is 5 ms at c3: one host hiccup moved it 10 %+)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-seconds", type=float, default=30.0, help="bounded CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (the same steps serial, roofline and per-kernel "
+                         "times, isolated MPN, e2e pipeline, front-end and grouping legs, backbone, CPU baseline) and "
+                         "report them in the result line; the --no-* options drop legs from it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (construct_graph's tensors and the MPN's logits) as "
+                         "DIR/<name>.npy, float32 or float64 (rank r > 0: DIR/rank<r>/); at most 64 MB, larger arrays "
+                         "as a fixed seeded sample of their elements")
+    ap.add_argument("--cpu-seconds", type=float, default=30.0, help="bounded CPU-baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle legs")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the profiler, e2e, front-end, grouping and backbone legs")
     ap.add_argument("--no-backbone", action="store_true",
-                    help="skip the backbone leg (a random-weight HigherHRNet-w48 forward on the batch's 640 px images, "
-                         "torch / MIOpen bf16 channels-last, tools/hrnet_w48.py; its first call compiles MIOpen "
+                    help="with --full: skip the backbone leg (a random-weight HigherHRNet-w48 forward on the batch's "
+                         "640 px images, torch / MIOpen bf16 channels-last, tools/hrnet_w48.py; its first call compiles MIOpen "
                          "kernels for ~7 s)")
     ap.add_argument("--profile-steps", action="store_true",
                     help="for rocprofv3 per-shape traces: the warmup and the K steps strictly serial on one stream "
@@ -88,7 +100,10 @@ def parse():
                     help="batches in flight: step i runs on HIP stream i %% S (serving-style overlap of one "
                          "batch's detection with the previous batch's MPN); 1 = strictly serial steps; 0 (default) "
                          "= the faster of 2 and 1, chosen by timing both schedules outside the timed region")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def setup_dist(n_gpus):
@@ -189,12 +204,15 @@ def run_steps(n, streams, S, wl, gc, model, hm, feats, tags, dev):
     is queued (construct_graph_start: detection, capacity graph build, MPN) before step i is collected
     (PendingGraph.result: the count wait, the output views, the model call returning the queued logits), so the
     host's count wait overlaps the next step's launches; each stream then has at most one step pending. S == 1:
-    run_step one after the other."""
+    run_step one after the other. Returns what the last step returned, (out, pe, pn, pc) as run_step does."""
+    last = None
     if S == 1 or os.environ.get("PEMP_BENCH_NO_PIPELINE"):   # (the latter: round 5's loop, for A/B runs)
         for i in range(n):
             with torch.cuda.stream(streams[i % S]):
-                run_step(wl, gc, model, hm, feats, tags, dev)
-        return
+                res = run_step(wl, gc, model, hm, feats, tags, dev)
+            if i == n - 1:
+                last = res
+        return last
     pend = None
     for i in range(n + 1):
         nxt = None
@@ -207,8 +225,44 @@ def run_steps(n, streams, S, wl, gc, model, hm, feats, tags, dev):
         if pend is not None:
             with torch.cuda.stream(pend[1]):
                 out = pend[0].result()
-                model(out[0], out[1], out[2], node_types=out[7][:, 2])
+                pe, pn, pc, _ = model(out[0], out[1], out[2], node_types=out[7][:, 2])
+            if i == n:
+                last = (out, pe, pn, pc)
         pend = nxt
+    return last
+
+
+DUMP_BUDGET = 60 << 20     # bytes of .npy payload --dump-outputs writes at most (the limit is 64 MB)
+GRAPH_OUTPUTS = ((0, "x"), (1, "edge_attr"), (2, "edge_index"), (7, "joint_det"), (11, "joint_scores"),
+                 (12, "batch_index"), (14, "joint_tags"))   # the tensors of construct_graph's 15-tuple
+
+
+def dump_outputs(path, last, rank):
+    """--dump-outputs: one step's results (run_steps' return) as <path>/<name>.npy. float32 tensors stay float32,
+    integer tensors (indices, detections) become float64, which holds them exactly. Whole arrays while they fit
+    DUMP_BUDGET together; otherwise an array over its share of it is written as a sample of its flattened elements
+    at sorted indices drawn by numpy.random.default_rng(0), the same indices in every run of the same shapes."""
+    out, pe, pn, pc = last
+    named = [(name, out[i]) for i, name in GRAPH_OUTPUTS]
+    for name, seq in (("edge_logits", pe), ("node_logits", pn), ("class_logits", pc)):
+        named += [(f"{name}_{k}", t) for k, t in enumerate(seq)]
+    named = [(name, t) for name, t in named if t is not None]
+    if rank:
+        path = os.path.join(path, f"rank{rank}")
+    os.makedirs(path, exist_ok=True)
+    arrays = []
+    for name, t in named:
+        a = t.detach().cpu().numpy()
+        arrays.append((name, np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)))
+    arrays.sort(key=lambda na: na[1].nbytes)   # smallest first: an array's share is what the smaller ones left over
+    left = DUMP_BUDGET
+    for k, (name, a) in enumerate(arrays):
+        share = left // (len(arrays) - k)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 _BENCH_MAPS = None
@@ -872,6 +926,8 @@ def pose_refine(wl, persons, cpu_ref):
 
 def main():
     args = parse()
+    if not args.full:   # a plain run: the timed steps alone, none of the legs beside them
+        args.no_roofline = args.no_cpu_baseline = args.no_backbone = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
     rank, world, dev = setup_dist(args.gpus)
@@ -935,7 +991,7 @@ def main():
         schedule_probe = {f"streams_{k}_ms_per_step": round(v * 1e3, 3) for k, v in probe.items()}
         schedule_probe["steps_per_trial"] = n_probe
 
-    # warmup (also finds the dominant kernel with the profiler on for every kernel)
+    # warmup (--full: also finds the dominant kernel with the profiler on for every kernel)
     dominant = dominant_overall = None
     for w in range(max(args.warmup, 1)):
         if w == max(args.warmup, 1) - 1 and not args.no_roofline:
@@ -960,16 +1016,19 @@ def main():
     barrier(world)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_steps(args.steps, streams, S, wl, gc, model, hm, feats, tags, dev)
+    last = run_steps(args.steps, streams, S, wl, gc, model, hm, feats, tags, dev)
     torch.cuda.synchronize()
     barrier(world)
     dt = time.perf_counter() - t0
     dt_max = max_over_ranks(dt, world, dev)
     imgs = wl["B"] * args.steps * world
     value = imgs / dt_max
+    if args.dump_outputs:   # (before any other leg reuses the streams' scratch the outputs may live in)
+        dump_outputs(args.dump_outputs, last, rank)
+    del last
     # the same K steps strictly serial on one stream (reported beside value)
     value_serial = None
-    if S > 1:
+    if S > 1 and args.full:
         barrier(world)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -997,20 +1056,22 @@ def main():
         _lib.prof_enable(None)
 
     # isolated MPN (same graphs): edge-updates/s
-    x, ea, ei, types = out[0], out[1], out[2], out[7][:, 2]
-    with torch.no_grad():
-        for _ in range(2):
-            model(x, ea, ei, node_types=types)
-    barrier(world)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    with torch.no_grad():
-        for _ in range(args.steps):
-            model(x, ea, ei, node_types=types)
-    torch.cuda.synchronize()
-    barrier(world)
-    dt_mpn = max_over_ranks(time.perf_counter() - t1, world, dev)
-    mpn_eups = E_all * wl["steps"] * args.steps / dt_mpn
+    dt_mpn = mpn_eups = None
+    if args.full:
+        x, ea, ei, types = out[0], out[1], out[2], out[7][:, 2]
+        with torch.no_grad():
+            for _ in range(2):
+                model(x, ea, ei, node_types=types)
+        barrier(world)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        with torch.no_grad():
+            for _ in range(args.steps):
+                model(x, ea, ei, node_types=types)
+        torch.cuda.synchronize()
+        barrier(world)
+        dt_mpn = max_over_ranks(time.perf_counter() - t1, world, dev)
+        mpn_eups = E_all * wl["steps"] * args.steps / dt_mpn
 
     e2e = e2e_pipeline(wl, gc, model, hm, feats, tags, dev, args.steps, args.warmup, world) \
         if not args.no_roofline else None
@@ -1020,7 +1081,8 @@ def main():
     front_hm = frontend_heatmaps(wl, gc, feats, dev) if single and not args.no_roofline else None
 
     global _BENCH_MAPS
-    _BENCH_MAPS = dense_maps(hm, tags)
+    if not args.no_roofline:
+        _BENCH_MAPS = dense_maps(hm, tags)
     grouping = pose_grouping(wl, out, pe, pn, pc, rank == 0 and world == 1 and not args.no_cpu_baseline) \
         if not args.no_roofline else None
     if grouping is not None and world > 1:
@@ -1047,7 +1109,8 @@ def main():
     bb = None
     if not args.no_backbone and not args.no_roofline:
         try:   # (an informational leg: never lose the bench line over it)
-            bb = backbone_leg(wl, dev, args.steps, dt_max / args.steps, world)
+            # (at most 100 forwards: one takes ~80 steps' time, so a long --steps would spend minutes here)
+            bb = backbone_leg(wl, dev, min(args.steps, 100), dt_max / args.steps, world)
         except Exception as exc:
             bb = {"error": repr(exc)[:200]}
 
@@ -1055,6 +1118,7 @@ def main():
         rec = {
             "metric": METRIC, "value": round(value, 2), "unit": "images/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt_max / args.steps * 1e3, 3),
+            "full": args.full,   # False: the fields of the other legs below are null (they run with --full)
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": model.precision,
             "data": "synthetic (seeded planted-Gaussian heatmaps, random features; closed-form MPN weights)",
@@ -1070,8 +1134,8 @@ def main():
             # the whole post-backbone step of valid.py (grouping and finishing included), pipelined over batches
             "e2e_images_per_sec": e2e["images_per_sec"] if e2e else None,
             "e2e": e2e,
-            "mpn_edge_updates_per_sec": round(mpn_eups, 1),
-            "mpn_ms_per_step": round(dt_mpn / args.steps * 1e3, 3),
+            "mpn_edge_updates_per_sec": round(mpn_eups, 1) if args.full else None,
+            "mpn_ms_per_step": round(dt_mpn / args.steps * 1e3, 3) if args.full else None,
             "pipeline_edge_updates_per_sec": round(E_all * wl["steps"] * args.steps / dt_max, 1),
             "roofline": roof,
             "kernel_avg_us": breakdown if not args.no_roofline else None,
