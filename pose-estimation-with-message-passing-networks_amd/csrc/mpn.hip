@@ -1441,18 +1441,29 @@ struct Chunks {
   bool head, tail;
 };
 
-__device__ __forceinline__ Chunks chunks_of(int seg, int c) {
-  const int prev = dppi<DPP_SHR1>(seg, INT_MIN), next = dppi<DPP_SHL1>(seg, INT_MIN);
+// The chunk structure is static across the passes of a forward (it follows from the sorted target list and the tile
+// origins of the range table), so it is not scanned out of the targets in every tile: edge_ranges_kernel leaves each
+// edge's position in its (target, type) segment in the spare high byte of its s_dst entry (node ids stay below 2^23,
+// pemp_mpn_forward's range check) -- bits 28-31 the distance to the segment's first edge, bits 24-27 the distance to
+// its last, each clamped to 15, which loses nothing: a tile only needs min(pos, c) and min(rem, last lane - c).
+constexpr int SDST_ID_BITS = 24, SDST_ID_MASK = (1 << SDST_ID_BITS) - 1;
+constexpr int64_t MPN_MAX_NODES = 1ll << 23;   // (also keeps the passes' 32-bit byte offsets in range)
+static_assert(MPN_MAX_NODES <= (1ll << SDST_ID_BITS), "node ids must leave the high byte of an s_dst entry free");
+__device__ __forceinline__ int sdst_id(int e) { return e & SDST_ID_MASK; }
+__device__ __forceinline__ int sdst_pack(int id, int pos, int rem) {
+  return (id & SDST_ID_MASK) | (min(max(rem, 0), 15) << SDST_ID_BITS) | (int)((unsigned)min(max(pos, 0), 15) << 28);
+}
+
+// e = the lane's packed s_dst entry, c = its lane in the row, lastc = the tile's last lane inside the wave's range
+// (uniform; 15 except in a range's last tile: a segment that runs on past the range end is cut there). Lanes past
+// the range end (!valid) are singleton chunks.
+__device__ __forceinline__ Chunks chunks_of(int e, int c, int lastc, bool valid) {
+  const int pos = (int)((unsigned)e >> 28), rem = (e >> SDST_ID_BITS) & 15;
   Chunks k;
-  k.head = prev != seg;
-  k.tail = next != seg;
-  int hs = k.head ? c : 0, te = k.tail ? c : 15;
-  hs = max(hs, dppi<DPP_SHR1>(hs, 0)); te = min(te, dppi<DPP_SHL1>(te, 15));
-  hs = max(hs, dppi<DPP_SHR2>(hs, 0)); te = min(te, dppi<DPP_SHL2>(te, 15));
-  hs = max(hs, dppi<DPP_SHR4>(hs, 0)); te = min(te, dppi<DPP_SHL4>(te, 15));
-  hs = max(hs, dppi<DPP_SHR8>(hs, 0)); te = min(te, dppi<DPP_SHL8>(te, 15));
-  k.d = c - hs;
-  k.u = te - c;
+  k.d = valid ? min(pos, c) : 0;
+  k.u = max(min(rem, lastc - c), 0);   // (lastc - c < 0 past the range end)
+  k.head = k.d == 0;
+  k.tail = k.u == 0;
   return k;
 }
 
@@ -1667,8 +1678,8 @@ __device__ inline int4 edge_wave_range(const int* __restrict__ seg, const int* _
   const int64_t tiles_t = (te - ts + 15) / 16;
   auto snap = [&](int p) -> int {               // first segment start at or after p
     if (p <= ts || p >= te) return min(p, te);
-    const int dp = min(max(s_dst[p], 0), (int)N - 1);   // (clamped: in range for any prepared list)
-    return dp == s_dst[p - 1] ? seg[t * N + dp + 1] : p;
+    const int dp = min(sdst_id(s_dst[p]), (int)N - 1);   // (clamped: in range for any prepared list)
+    return dp == sdst_id(s_dst[p - 1]) ? seg[t * N + dp + 1] : p;
   };
   const int lo = snap(ts + 16 * (int)(tiles_t * j / gt)), hi = snap(ts + 16 * (int)(tiles_t * (j + 1) / gt));
   const int ntile = (hi - lo + 15) / 16;
@@ -1677,27 +1688,46 @@ __device__ inline int4 edge_wave_range(const int* __restrict__ seg, const int* _
   const int first = min(hi, lo + 16 * a0), end = min(hi, lo + 16 * a1);
   int flags = 0;
   if (first < end) {
-    if (first > lo && s_dst[first - 1] == s_dst[first]) flags |= RANGE_CONT_IN;
-    if (end < hi && s_dst[end - 1] == s_dst[end]) flags |= RANGE_CONT_OUT;
-    if (s_dst[first] == s_dst[end - 1]) flags |= RANGE_ONE_SEG;
+    if (first > lo && sdst_id(s_dst[first - 1]) == sdst_id(s_dst[first])) flags |= RANGE_CONT_IN;
+    if (end < hi && sdst_id(s_dst[end - 1]) == sdst_id(s_dst[end])) flags |= RANGE_CONT_OUT;
+    if (sdst_id(s_dst[first]) == sdst_id(s_dst[end - 1])) flags |= RANGE_ONE_SEG;
   }
   return make_int4(first, end, t, flags);
 }
 
 // ranges for the middle passes (EDGE_WAVES waves) then the recorded passes (edge_waves<1>()), G blocks
 __device__ inline void edge_ranges_fill(const int* seg, const int* wg_start, const int* s_dst, int T, int64_t N, int G,
-                                        int4* __restrict__ ranges) {
+                                        int4* __restrict__ ranges, int blk, int nblk) {
   const int n_mid = G * EDGE_WAVES, n_all = n_mid + G * edge_waves<1>();
-  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < n_all; q += gridDim.x * blockDim.x) {
+  for (int q = blk * blockDim.x + threadIdx.x; q < n_all; q += nblk * blockDim.x) {
     const int NW = q < n_mid ? EDGE_WAVES : edge_waves<1>(), r = q < n_mid ? q : q - n_mid;
     ranges[q] = edge_wave_range(seg, wg_start, s_dst, T, N, r / NW, r % NW, NW);
   }
 }
 
-__global__ __launch_bounds__(256) void edge_ranges_kernel(const int* seg, const int* wg_start, const int* s_dst, int T,
-                                                          int64_t N, int G, int4* ranges, const int64_t* ne) {
+// Each edge's position in its (target, type) segment into the high byte of its s_dst entry (sdst_pack; read by
+// chunks_of in every tile of every pass). One thread per edge, read off the segment table, so it holds for both
+// range tables and after every prepare path; a list prepared by an earlier call is packed again to the same bits.
+// The range table's threads read neighbouring entries while this runs: they look at the id bits only, which are
+// rewritten unchanged (aligned 32-bit stores).
+__device__ inline void edge_positions_fill(const int* __restrict__ seg, int* s_dst, int T, int64_t N, int blk, int nblk) {
+  const int etot = seg[T * N];
+  for (int p = blk * blockDim.x + threadIdx.x; p < etot; p += nblk * blockDim.x) {
+    const int e = s_dst[p], dp = min(sdst_id(e), (int)N - 1);
+    int t = 0;
+    for (int k = 1; k < T; ++k) t += seg[k * N] <= p ? 1 : 0;   // (uniform loads)
+    const int s0 = seg[t * N + dp], s1 = seg[t * N + dp + 1];
+    s_dst[p] = sdst_pack(e, p - s0, s1 - 1 - p);
+  }
+}
+
+// The first RB blocks fill the range tables, the others the segment positions (two short chains of dependent loads
+// side by side instead of one after the other).
+__global__ __launch_bounds__(256) void edge_ranges_kernel(const int* seg, const int* wg_start, int* s_dst, int T,
+                                                          int64_t N, int G, int4* ranges, const int64_t* ne, int RB) {
   if (ne) N = ne[0];   // capacity mode: the device-side node count (N: the capacity)
-  edge_ranges_fill(seg, wg_start, s_dst, T, N, G, ranges);
+  if ((int)blockIdx.x < RB) edge_ranges_fill(seg, wg_start, s_dst, T, N, G, ranges, blockIdx.x, RB);
+  else edge_positions_fill(seg, s_dst, T, N, blockIdx.x - RB, gridDim.x - RB);
 }
 
 // 16-byte LDS-DMA load per lane into the wave-contiguous LDS block at `l` (lane i -> l + 16 i bytes).
@@ -1844,7 +1874,7 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
   float4 xa[4], xb[4], xp[4];
   int orig_t = 0;
   auto gather_nt = [&](int dstv, int srcv, bool on) {
-    const int va = on ? dstv * nt_row + 16 * g : OOB_VOFF, vb = on ? srcv * nt_row + 256 + 16 * g : OOB_VOFF;
+    const int va = on ? sdst_id(dstv) * nt_row + 16 * g : OOB_VOFF, vb = on ? srcv * nt_row + 256 + 16 * g : OOB_VOFF;
 #pragma unroll
     for (int ob = 0; ob < 4; ++ob) {
       xa[ob] = bld4(rs_nt, va + 64 * ob);
@@ -1879,7 +1909,7 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
   EDGE_STAMP(1);
   EDGE_STAMP(2);
   // target of the segment begun by the previous wave (lane 0 of the first tile's indices; wave-uniform)
-  const int seg_first = (rflags & RANGE_CONT_IN) ? __builtin_amdgcn_readfirstlane(dst_n) : -1;
+  const int seg_first = (rflags & RANGE_CONT_IN) ? sdst_id(__builtin_amdgcn_readfirstlane(dst_n)) : -1;
   const rsrc_t rs_next = make_rsrc(a.r_next, E * 256);
   const rsrc_t rs_agg = make_rsrc(a.agg, (int)a.N * T * 256);
   const u32x4v_s rw_r = rsrc_words(a.r_cur, end * 256);
@@ -2007,8 +2037,8 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
     }
     // chunk structure of the tile and each edge's softmax weight pe = exp(a - M), M = its segment's maximum so far
     // (computed before the message GEMMs: with PE_FOLD it rides in the split of m)
-    const int seg = valid ? dst : -1 - c;        // padding lanes: singleton chunks, never written
-    const Chunks ck = chunks_of(seg, c);
+    const int seg = valid ? sdst_id(dst) : -1 - c;   // padding lanes: singleton chunks, never written
+    const Chunks ck = chunks_of(dst, c, min(end - 1 - base, 15), valid);
     const bool carry_in = have_carry;            // wave-uniform: set only when the segment continues
     float M = 0.f, pe = 1.0f;
     if (AGG == PEMP_AGGR_ATTN) {
@@ -2139,7 +2169,7 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
     }
     // the chunk at the tile end continues iff the next tile starts with the same target
     const int seg15 = __builtin_amdgcn_readlane(seg, 15);
-    const bool carry_out = more && __builtin_amdgcn_readlane(dst_n, 0) == seg15;
+    const bool carry_out = more && sdst_id(__builtin_amdgcn_readlane(dst_n, 0)) == seg15;
     if (carry_out) {
       cl = readlane_f(l, 15);
       cM = readlane_f(M, 15);
@@ -2213,7 +2243,7 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
     }
     const float inv = ((AGG == PEMP_AGGR_ATTN) ? 1.0f / (l + 1e-12f) : (AGG == PEMP_AGGR_MEAN) ? 1.0f / l : 1.0f) *
                       dom_inv<PREC>();
-    const int seg_last = __builtin_amdgcn_readfirstlane(a.s_dst[end - 1]);
+    const int seg_last = sdst_id(__builtin_amdgcn_readfirstlane(a.s_dst[end - 1]));
     a.agg[((int64_t)seg_last * T + t) * 64 + lane] = v * inv;
   }
   EDGE_STAMP(15);
@@ -3902,9 +3932,11 @@ static int mpn_forward_impl(const pemp_mpn_desc* desc, const pemp_mpn_weights* w
   const int T = desc->num_types, J = desc->num_joints;
   PEMP_CHECK_ARG(desc->hidden == 64, "pemp_mpn_forward: hidden width must be 64 (got %d)", desc->hidden);
   PEMP_CHECK_ARG(T >= 1 && T <= MAXT, "pemp_mpn_forward: num_types must be in [1, %d]", MAXT);
-  // (the edge passes address r, Q0 and the aggregates with 32-bit byte offsets: E, T N < 2^23)
-  PEMP_CHECK_ARG(N >= 0 && E >= 0 && N < (1ll << 23) && E < (1ll << 23) && (int64_t)T * N < (1ll << 23),
-                 "pemp_mpn_forward: N=%lld E=%lld out of range", (long long)N, (long long)E);
+  // (the edge passes address r, Q0 and the aggregates with 32-bit byte offsets: E, T N < 2^23; the sorted target
+  // list carries each edge's segment position above its node id, MPN_MAX_NODES)
+  PEMP_CHECK_ARG(N >= 0 && E >= 0 && N < MPN_MAX_NODES && E < (1ll << 23) && (int64_t)T * N < (1ll << 23),
+                 "pemp_mpn_forward: N=%lld E=%lld out of range (N, E and num_types * N must stay below 2^23)",
+                 (long long)N, (long long)E);
   PEMP_CHECK_ARG(desc->steps >= 0 && desc->aux_loss_steps >= 0, "pemp_mpn_forward: bad steps");
   PEMP_CHECK_ARG(desc->aggr >= PEMP_AGGR_ATTN && desc->aggr <= PEMP_AGGR_MAX, "pemp_mpn_forward: bad aggr");
   PEMP_CHECK_ARG(desc->aggr != PEMP_AGGR_ATTN || w->attn_w, "pemp_mpn_forward: attention needs attn_w");
@@ -4048,8 +4080,11 @@ static int mpn_forward_impl(const pemp_mpn_desc* desc, const pemp_mpn_weights* w
   // the passes' per-wave range table (static across iterations), right behind the order on the prelude stream:
   // its chains of dependent small loads stay off the edge embedding's workgroups
   if (E > 0 && steps >= 1) {
-    hipLaunchKernelGGL(edge_ranges_kernel, dim3((unsigned)std::min(64, (edge_grid * (EDGE_WAVES + 12) + 255) / 256)),
-                       dim3(256), 0, pst, ws.seg, ws.wg_start, ws.s_dst, T, N, edge_grid, ws.ranges, ne);
+    // (behind the range table's blocks: the per-edge segment positions, one edge per thread)
+    const int rg_blocks = std::min(64, (edge_grid * (EDGE_WAVES + 12) + 255) / 256);
+    const int pos_blocks = (int)std::min<int64_t>(1024, (E + 255) / 256);
+    hipLaunchKernelGGL(edge_ranges_kernel, dim3((unsigned)(rg_blocks + pos_blocks)), dim3(256), 0, pst, ws.seg,
+                       ws.wg_start, ws.s_dst, T, N, edge_grid, ws.ranges, ne, rg_blocks);
     PEMP_LAUNCH_CHECK();
   }
   return PEMP_OK;

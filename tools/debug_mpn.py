@@ -64,7 +64,7 @@ def main(variant="add", steps=1, gname="gc_small_fully"):
     src_t = types if T > 1 else torch.zeros_like(types)
     key = src_t[ei[0]] * N + ei[1]
     print("sorted keys monotone:", bool((key[s_orig][1:] >= key[s_orig][:-1]).all()))
-    print("s_src ok:", torch.equal(w["s_src"].long(), ei[0][s_orig]), "s_dst ok:", torch.equal(w["s_dst"].long(), ei[1][s_orig]))
+    print("s_src ok:", torch.equal(w["s_src"].long(), ei[0][s_orig]), "s_dst ok:", torch.equal(w["s_dst"].long() & 0xFFFFFF, ei[1][s_orig]))
 
     x0 = restate._mlp(sd, "node_embedding", x, cfg.NODE_EMB.OUTPUT_SIZES, True)
     e0 = restate._mlp(sd, "edge_embedding", ea, cfg.EDGE_EMB.OUTPUT_SIZES, True)
