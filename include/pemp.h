@@ -24,6 +24,8 @@
  *   pemp_gather_projected_conv  the same with feature_gather (PoseEstimation.py:64-66, 341) at the taps only
  *   pemp_pose_*          Utils.py:499-514,672-743,1445-1455 pose grouping (pred_to_ann prefix, pred_to_person,
  *                        GAEC of correlation_clustering_utils.py:187-245, graph_cluster_to_persons)
+ *   pemp_label_*         ConstructGraph.py:627-694,769-942,1096-1158 training labels of EDGE_LABEL_METHOD 4 / 6
+ *                        (_construct_edge_labels_4 / _6, match_cc, create_loss_mask)
  *   pemp_mpn_forward     Models/MessagePassingNetwork/NodeClassificationMPNSimple.py:62-97 with
  *                        layers.py:32-86 (MPLayer) / :157-274 (TypeAwareMPNLayer)
  */
@@ -37,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PEMP_ABI_VERSION 20
+#define PEMP_ABI_VERSION 21
 
 enum {
   PEMP_OK = 0,
@@ -621,6 +623,56 @@ int pemp_mpn_status(const pemp_mpn_desc* desc, int64_t N, int64_t E, const void*
  * one event pair, so the per-launch average excludes the event-record overhead (count += R). */
 int pemp_prof_enable(const char* filter);
 int pemp_prof_report(char* buf, size_t len);
+
+/* ------------------------------------------------------------------------------------------
+ * Training labels, EDGE_LABEL_METHOD 4 and 6 (ConstructGraph.py:627-694 _construct_edge_labels_4, :769-942
+ * _construct_edge_labels_6 with its method == 2, :1096-1158 match_cc / create_loss_mask, :145-146).
+ *
+ * 1. pemp_label_candidates (GPU, stream-ordered): per image the visible ground-truth joints (joints_gt
+ *    [B, P, J, 3] f32 (x, y, visible), visible != 0) in (person, joint) order: gt_tab[b][g] = person * J + joint,
+ *    hdr[B + b] = G_b. For every (g, n) of the image, n its detection (joint_det [N, 3] int64 (x, y, type),
+ *    node_off [B + 1] int64): sim = exp(-d2 / factors[b][person][joint]) with d2 = (clamp(rint(gt_x), 0,
+ *    max(H, W)) - det_x)^2 + (likewise y)^2 in f32; the division and the exponential in f32 for f32 factors,
+ *    in f64 for f64 factors (factors_f64 != 0), as torch promotes. The pairs with sim >= threshold are stored
+ *    in (g, n) order at recs[b * cap + i], hdr[b] = their count. An image with more than cap pairs stores
+ *    none and sets hdr[2 B] = 1 (hdr[b] is still the count: call again with cap >= max hdr[b]). hdr: int32
+ *    [2 B + 1]; gt_tab: int32 [B, P J]; scratch: pemp_label_candidates_scratch_size(B, P, J) bytes.
+ * 2. pemp_label_assign (HOST arrays: copies of hdr, gt_tab, recs; node_off_host [B + 1]): per image the
+ *    maximum-weight assignment over the same-type pairs with sim >= matching_radius (nonzero part of the
+ *    reference's dense scipy solve), for method 6 a second one over the different-type pairs that fills the
+ *    rows the first left unmatched; with use_neighbours the unmatched detections whose only pair with
+ *    sim >= inclusion_radius (method 4: same type and >= both radii) belongs to a matched row join it, the
+ *    ones with several such pairs are ambiguous. Outputs [N]: node_labels (1 matched), node_persons (-1
+ *    unmatched), node_classes (gt joint type; J for unmatched nodes with with_background), label_mask_node
+ *    (0 on ambiguous nodes, method 6), class_mask (node_labels * label_mask_node, ones with
+ *    with_background), ambiguous (byte). node_classes / class_mask may be NULL for method 4. Pairs are
+ *    written in the reference's order, so a detection matched twice keeps its last pair. A ground-truth row
+ *    count above the detection count follows the same row rule (the reference is ill-defined there).
+ *    Returns PEMP_LABEL_OVERFLOW (and writes nothing) when hdr[2 B] is set.
+ * 3. pemp_label_edges (GPU, stream-ordered): edge_index [2, E] int64 of the batch, the images one after the
+ *    other. edge_labels[e] = 1 iff both ends are matched to the same person; label_mask[e] = 0 iff an end is
+ *    ambiguous, or the edge's image has no edge with label 1. node_persons / ambiguous: device copies of
+ *    step 2's outputs. scratch: pemp_label_edges_scratch_size(B) bytes. Deterministic.
+ * ---------------------------------------------------------------------------------------- */
+#define PEMP_LABEL_OVERFLOW 1
+typedef struct pemp_label_cand {
+  int32_t g;      /* row: index into the image's gt_tab */
+  uint32_t n;     /* bits 0-30: detection index inside the image; bit 31: same joint type */
+  double sim;
+} pemp_label_cand;
+size_t pemp_label_candidates_scratch_size(int B, int P, int J);
+int pemp_label_candidates(const float* joints_gt, const void* factors, int factors_f64, int B, int P, int J,
+                          const int64_t* joint_det, const int64_t* node_off, int H, int W, double threshold,
+                          int64_t cap, pemp_label_cand* recs, int32_t* hdr, int32_t* gt_tab, void* scratch,
+                          size_t scratch_bytes, void* stream);
+int pemp_label_assign(int B, int P, int J, const int32_t* hdr, const int32_t* gt_tab, const pemp_label_cand* recs,
+                      int64_t cap, const int64_t* node_off_host, int method, int use_neighbours, int with_background,
+                      double matching_radius, double inclusion_radius, float* node_labels, int64_t* node_persons,
+                      int64_t* node_classes, float* label_mask_node, float* class_mask, uint8_t* ambiguous);
+size_t pemp_label_edges_scratch_size(int B);
+int pemp_label_edges(const int64_t* edge_index, int64_t E, const int64_t* node_off, int B, int64_t N,
+                     const int64_t* node_persons, const uint8_t* ambiguous, float* edge_labels, float* label_mask,
+                     void* scratch, size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ import os
 
 LIB_PATH = os.environ.get("PEMP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc",
                                                      "libpemp.so")
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 ERR_INVALID_ARG, ERR_HIP, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -3, -4
 BUILD_WRITE_COUNTS = 0x100          # pemp.h PEMP_BUILD_WRITE_COUNTS
@@ -140,7 +140,16 @@ SIGNATURES = {
     "pemp_step_fully_cap": (c_i32, [ctypes.POINTER(PempStepPlan), c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pemp_prof_enable": (c_i32, [ctypes.c_char_p]),
     "pemp_prof_report": (c_i32, [ctypes.c_char_p, c_sz]),
+    "pemp_label_candidates_scratch_size": (c_sz, [c_i32, c_i32, c_i32]),
+    "pemp_label_candidates": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_i32, ctypes.c_double,
+                                      c_i64, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "pemp_label_assign": (c_i32, [c_i32, c_i32, c_i32, c_p, c_p, c_p, c_i64, c_p, c_i32, c_i32, c_i32,
+                                  ctypes.c_double, ctypes.c_double, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pemp_label_edges_scratch_size": (c_sz, [c_i32]),
+    "pemp_label_edges": (c_i32, [c_p, c_i64, c_p, c_i32, c_i64, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
+LABEL_OVERFLOW = 1                  # pemp.h PEMP_LABEL_OVERFLOW
+LABEL_CAND_DTYPE = [("g", "<i4"), ("n", "<u4"), ("sim", "<f8")]   # pemp.h pemp_label_cand
 
 _LIB = None
 

@@ -1,4 +1,6 @@
-"""Drop-in ``NaiveGraphConstructor`` (``src/graph_constructor/ConstructGraph.py:9-249``), inference path.
+"""Drop-in ``NaiveGraphConstructor`` (``src/graph_constructor/ConstructGraph.py:9-249``): the inference path, and
+with ``joints_gt`` the training labels of EDGE_LABEL_METHOD 4 and 6 (``pemp_label_candidates`` /
+``pemp_label_assign`` / ``pemp_label_edges``).
 
 Same constructor signature, same ``construct_graph()`` 15-tuple, same dtypes (int64 indices) and
 node/edge order as the reference; computed by ``libpemp.so`` (``pemp_detect``,
@@ -30,6 +32,10 @@ _EF_MODES = {
     frozenset(["ae_tracking_1"]): 8,
 }
 _EF_TAG_MODES = (5, 6, 7, 8)
+
+
+def _align256(n):
+    return (n + 255) // 256 * 256
 
 
 def _tag_fully(edge_index, node_off, counts, joint_det):
@@ -230,9 +236,6 @@ class NaiveGraphConstructor:
 
     def __init__(self, scoremaps, tagmaps, features, joints_gt, factor_list, masks, device, config, testing,
                  heatmaps, num_joints):
-        if joints_gt is not None:
-            raise NotImplementedError("training-time label construction (joints_gt) is out of scope: "
-                                      "ConstructGraph.py:114-176 runs only with ground truth")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("pemp_amd NaiveGraphConstructor runs on the HIP device only (no CPU fallback)")
@@ -240,7 +243,7 @@ class NaiveGraphConstructor:
         self.tagmaps = tagmaps.to(self.device) if tagmaps is not None else None
         self.features = features.to(self.device)
         self.masks = masks.to(self.device) if masks is not None else None
-        self.joints_gt = None
+        self.joints_gt = joints_gt
         self.factor_list = factor_list
         self.batch_size = scoremaps.shape[0]
         self.num_joints = num_joints
@@ -253,7 +256,107 @@ class NaiveGraphConstructor:
         self.pool_kernel_size = config.POOL_KERNEL_SIZE
         self.testing = testing
         if getattr(config, "USE_GT", False) or getattr(config, "IMAGE_CENTRIC_SAMPLING", False):
-            raise NotImplementedError("USE_GT / IMAGE_CENTRIC_SAMPLING need ground truth (training only)")
+            raise NotImplementedError("USE_GT / IMAGE_CENTRIC_SAMPLING need ground truth (training only): USE_GT replaces "
+                                      "the detections (ConstructGraph.py:76-87, 114-122), IMAGE_CENTRIC_SAMPLING draws "
+                                      "a random subgraph (ConstructGraph.py:182-204)")
+        self._labels = None if joints_gt is None else self._label_setup(config)
+
+    # ---- training labels (EDGE_LABEL_METHOD 4 / 6; ConstructGraph.py:123-149, 627-694, 769-942, 1096-1158) ----
+    _label_cap = 1024        # candidate records per image kept between calls (grows on overflow, under _mu)
+
+    def _label_setup(self, config):
+        """Reads the label options with the reference's meaning, refuses the ones that are not built, and moves
+        joints_gt [B, P, J, 3] / factor_list [B, P, J] to the device (ConstructGraph.py:16-17, 23-44)."""
+        method = config.EDGE_LABEL_METHOD
+        if method not in (4, 6):
+            raise NotImplementedError(f"EDGE_LABEL_METHOD={method}: methods 4 and 6 are built (_construct_edge_labels_4 "
+                                      "/ _6, ConstructGraph.py:627-694, 769-942); 1, 2, 3, 5 and 7 "
+                                      "(ConstructGraph.py:475-625, 696-767, 944-1093) are not")
+        if getattr(config, "NODE_DROPOUT", 0.0) != 0.0 and not self.testing:
+            raise NotImplementedError("NODE_DROPOUT != 0 with testing=False drops a random subgraph "
+                                      "(ConstructGraph.py:152-168): not built")
+        if getattr(config, "WEIGHT_CLASS_LOSS", False):
+            raise NotImplementedError("WEIGHT_CLASS_LOSS weights class_mask by the heatmap read at (y, type) instead of "
+                                      "(y, x) (ConstructGraph.py:171-176): not built")
+        gt = torch.as_tensor(self.joints_gt).to(self.device)
+        if gt.dim() != 4 or gt.shape[0] != self.batch_size or gt.shape[2] != self.num_joints or gt.shape[3] != 3:
+            raise ValueError(f"joints_gt {tuple(gt.shape)}: expected [{self.batch_size}, P, {self.num_joints}, 3]")
+        fac = self.factor_list
+        if fac is None:
+            raise TypeError("joints_gt is given but factor_list is None")   # reference: factor_list[batch] on None
+        if isinstance(fac, (list, tuple)):
+            fac = torch.stack([torch.as_tensor(f) for f in fac])
+        fac = torch.as_tensor(fac).to(self.device)
+        if tuple(fac.shape) != tuple(gt.shape[:3]):
+            raise ValueError(f"factor_list {tuple(fac.shape)}: expected {tuple(gt.shape[:3])}")
+        f64 = fac.dtype == torch.float64   # torch promotes -distance / factor to the factors' float64, else float32
+        self.joints_gt = gt
+        return dict(method=method, neighbours=bool(config.USE_NEIGHBOURS), background=bool(config.WITH_BACKGROUND),
+                    mr=float(config.MATCHING_RADIUS), ir=float(config.INCLUSION_RADIUS), f64=f64,
+                    gt=gt.float().contiguous(), fac=(fac if f64 else fac.float()).contiguous())
+
+    def _label_outputs(self, L, st, out, node_off, counts_l, B, H, W, dev):
+        """construct_graph's tuple with slots 3, 4, 5, 8, 9, 10 and 13 filled as ConstructGraph.py:232-249 does:
+        candidate pairs on the device (pemp_label_candidates), the matching on the host (pemp_label_assign; one
+        read-back of the sparse list, one upload of the per-node results), the edge pass on the device
+        (pemp_label_edges)."""
+        lp = self._labels
+        joint_det, edge_index = out[7], out[2]
+        N, E = joint_det.shape[0], edge_index.shape[1]
+        P, J = lp["gt"].shape[1], lp["gt"].shape[2]
+        PJ = P * J
+        mr, ir = lp["mr"], lp["ir"]
+        if not lp["f64"]:   # a float32 similarity is compared with the radius in float32
+            mr, ir = float(np.float32(mr)), float(np.float32(ir))
+        thr = min(mr, ir) if lp["neighbours"] else mr
+        node_off_h = np.zeros(B + 1, np.int64)
+        node_off_h[1:] = np.cumsum(np.asarray(counts_l, np.int64))
+        scratch = L.pemp_label_candidates_scratch_size(B, P, J)
+        with NaiveGraphConstructor._mu:
+            cap = NaiveGraphConstructor._label_cap
+        while True:
+            o_tab = _align256(4 * (2 * B + 1))
+            o_rec = o_tab + _align256(4 * B * PJ)
+            o_end = o_rec + _align256(16 * B * cap)
+            buf = torch.empty(o_end + scratch, dtype=torch.uint8, device=dev)
+            base = buf.data_ptr()
+            _lib.check(L.pemp_label_candidates(lp["gt"].data_ptr(), lp["fac"].data_ptr(), int(lp["f64"]), B, P, J,
+                                               _lib.ptr(joint_det), _lib.ptr(node_off), H, W, thr, cap, base + o_rec,
+                                               base, base + o_tab, base + o_end, scratch, st))
+            host = torch.empty(o_end, dtype=torch.uint8, pin_memory=True)
+            host.copy_(buf[:o_end], non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            hdr = host[:4 * (2 * B + 1)].view(torch.int32).numpy()
+            if not hdr[2 * B]:
+                break
+            cap = int(hdr[:B].max())       # overflow: nothing was stored, every image's need was counted
+            cap += cap // 4
+            with NaiveGraphConstructor._mu:
+                NaiveGraphConstructor._label_cap = cap = max(NaiveGraphConstructor._label_cap, cap)
+        m6 = lp["method"] == 6
+        res_h = torch.empty(max(29 * N, 1), dtype=torch.uint8, pin_memory=True)
+        hp = res_h.data_ptr()
+        hb = host.data_ptr()
+        rc = L.pemp_label_assign(B, P, J, hb, hb + o_tab, hb + o_rec, cap, node_off_h.ctypes.data, lp["method"],
+                                 int(lp["neighbours"]), int(lp["background"]), mr, ir, hp + 16 * N, hp,
+                                 hp + 8 * N if m6 else None, hp + 20 * N, hp + 24 * N if m6 else None, hp + 28 * N)
+        _lib.check(rc)
+        res = torch.empty(max(29 * N, 1), dtype=torch.uint8, device=dev)
+        res.copy_(res_h, non_blocking=True)
+        node_persons = res[:8 * N].view(torch.int64)
+        node_classes = res[8 * N:16 * N].view(torch.int64) if m6 else None
+        node_labels = res[16 * N:20 * N].view(torch.float32)
+        label_mask_node = res[20 * N:24 * N].view(torch.float32)
+        class_mask = res[24 * N:28 * N].view(torch.float32) if m6 else None
+        ambiguous = res[28 * N:29 * N]
+        edge_labels = torch.empty(E, dtype=torch.float32, device=dev)
+        label_mask = torch.empty(E, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.pemp_label_edges_scratch_size(B), dtype=torch.uint8, device=dev)
+        _lib.check(L.pemp_label_edges(_lib.ptr(edge_index), E, _lib.ptr(node_off), B, N, _lib.ptr(node_persons),
+                                      _lib.ptr(ambiguous), _lib.ptr(edge_labels), _lib.ptr(label_mask), _lib.ptr(ws),
+                                      ws.numel(), st))
+        return (out[0], out[1], out[2], edge_labels, node_labels, node_classes, None, out[7], label_mask,
+                label_mask_node, class_mask, out[11], out[12], node_persons, out[14])
 
     # ------------------------------------------------------------------------------------
     def construct_graph(self):
@@ -341,7 +444,8 @@ class NaiveGraphConstructor:
         fully = self.mpn_graph_type == "fully" and B <= 1024 and not (proj_tags is not None and mode in _EF_TAG_MODES)
         gkey = (B, J, H, W, C, F, A, dev)
         with NaiveGraphConstructor._mu:
-            hint = NaiveGraphConstructor._graph_hint.get(gkey) if fully else None
+            # with ground truth always the exact build: the labels need the host counts before they start anyway
+            hint = NaiveGraphConstructor._graph_hint.get(gkey) if fully and self._labels is None else None
             cap = NaiveGraphConstructor._cap
         built = None
         pending = None
@@ -504,8 +608,11 @@ class NaiveGraphConstructor:
             joint_tags = joint_tags.view((N,) + tuple(tags.shape[4:])) if tags.dim() > 4 else joint_tags.view(N)
         if proj_tags is not None and fully:
             joint_tags = self._gather_proj_tags(L, st, proj_tags, J, H, W, joint_det, batch_index, N, dev)
-        return (x, edge_attr, edge_index, None, None, None, None, joint_det, None, None, None, joint_scores,
-                batch_index, None, joint_tags)
+        out = (x, edge_attr, edge_index, None, None, None, None, joint_det, None, None, None, joint_scores,
+               batch_index, None, joint_tags)
+        if self._labels is not None:
+            out = self._label_outputs(L, st, out, node_off, counts_l, B, H, W, dev)
+        return out
 
     @staticmethod
     def _update_hint(gkey, counts_l):

@@ -117,3 +117,64 @@ def closed_form_state_dict(module_or_sd, salt: float = 0.0, attn_gain: float = 1
             t = t * attn_gain
         out[k] = t.to(v.dtype)
     return out
+
+
+def make_labelled_heatmaps(seed: int, B: int, J: int, H: int, W: int, persons: int, sigma: float = 2.0,
+                           max_people: int = 30, margin: int = 12):
+    """Heatmaps with ground truth for the training labels (EDGE_LABEL_METHOD 4 / 6): (heatmaps [B,J,H,W] f32,
+    joints_gt [B,max_people,J,3] f32 (x, y, visible), factors [B,max_people,J] f64).
+
+    Per image `persons` people with planted peaks and one more without any (a missed person). Ground-truth positions
+    are the planted integer positions moved by a small integer jitter plus a sub-pixel offset; about a fifth of the
+    joints are invisible and a tenth of the visible ones have no peak. Three structures are planted per image so that
+    every label rule is exercised: a joint whose only nearby peak has another type (the different-type fill-in of
+    method 6), a second peak of the same type 4 px from a matched joint (a neighbour), and two people whose joints of
+    one type lie 8 px apart with a third peak between them (an ambiguous detection); 2 J more peaks are false positives. The last image of a batch of
+    more than one has peaks but no ground truth at all. Factors follow the dataset's (2 sigma_k)^2 * area * 2 with
+    sigma_k in [0.025, 0.107] and areas of 150 to 900 px, so similarities fall on both sides of the usual radii."""
+    rng = np.random.default_rng(seed)
+    hms = np.zeros((B, J, H, W), np.float32)
+    gt = np.zeros((B, max_people, J, 3), np.float32)
+    sig_k = np.linspace(0.025, 0.107, J)
+    factors = np.ones((B, max_people, J), np.float64)
+    for b in range(B):
+        area = rng.uniform(150.0, 900.0, max_people)
+        factors[b] = (2 * sig_k[None, :]) ** 2 * area[:, None] * 2
+        n_peak = (persons + 2) * J + 8
+        amps = 0.65 + 0.35 * rng.permutation(n_peak) / n_peak + rng.uniform(0, 0.1 / n_peak, n_peak)
+        pos = np.stack([rng.integers(margin, W - margin, (persons + 1, J)),
+                        rng.integers(margin, H - margin, (persons + 1, J))], -1)
+        peaks = []                                      # (type, x, y)
+        if b == B - 1 and B > 1:                        # no ground truth: peaks only
+            peaks = [(j, pos[p, j, 0], pos[p, j, 1]) for p in range(persons) for j in range(J)]
+        else:
+            vis = rng.random((persons + 1, J)) > 0.2
+            planted = vis & (rng.random((persons + 1, J)) > 0.1)
+            planted[persons] = False                    # the missed person
+            jit = rng.integers(-2, 3, (persons + 1, J, 2))
+            # the planted structures, on joints of the first two people
+            ja, jn, jm = rng.permutation(J)[:3]
+            vis[0, [ja, jn, jm]] = True
+            vis[1, jm] = True
+            planted[0, ja] = False                      # only a peak of another type nearby
+            planted[0, [jn, jm]] = True
+            planted[1, jm] = True
+            jit[0, [ja, jn, jm]] = 0
+            jit[1, jm] = 0
+            pos[1, jm] = pos[0, jm] + (8 if pos[0, jm, 0] + 8 < W - 4 else -8, 0)
+            factors[b, :2, [ja, jn, jm]] = rng.uniform(60.0, 90.0, (3, 2))
+            peaks.append(((ja + 1) % J, pos[0, ja, 0] + 1, pos[0, ja, 1]))
+            peaks.append((jn, pos[0, jn, 0], pos[0, jn, 1] + (4 if pos[0, jn, 1] + 4 < H - 4 else -4)))
+            peaks.append((jm, (pos[0, jm, 0] + pos[1, jm, 0]) // 2, pos[0, jm, 1]))
+            for p in range(persons + 1):
+                for j in range(J):
+                    if planted[p, j]:
+                        peaks.append((j, pos[p, j, 0], pos[p, j, 1]))
+            for j in range(2 * J):                      # false positives away from any structure's rule
+                peaks.append((j % J, int(rng.integers(margin, W - margin)), int(rng.integers(margin, H - margin))))
+            n_gt = persons + 1
+            gt[b, :n_gt, :, :2] = pos + jit + rng.uniform(-0.45, 0.45, (n_gt, J, 2))
+            gt[b, :n_gt, :, 2] = np.where(vis, rng.integers(1, 3, (n_gt, J)), 0)
+        for k, (j, x, y) in enumerate(peaks):
+            plant_peaks(hms[b, j:j + 1], np.array([[[x, y]]]), amps[k:k + 1, None], sigma)
+    return hms, gt, factors
