@@ -28,6 +28,9 @@
  *                        (_construct_edge_labels_4 / _6, match_cc, create_loss_mask)
  *   pemp_mpn_forward     Models/MessagePassingNetwork/NodeClassificationMPNSimple.py:62-97 with
  *                        layers.py:32-86 (MPLayer) / :157-274 (TypeAwareMPNLayer)
+ *   pemp_seg_*           the graph operators of the same layers in training: torch_scatter 2.0.4 scatter /
+ *                        scatter_softmax per (target, source type) (layers.py:226-251, PyG's aggregate for MPLayer)
+ *                        and the backward of the x[i] / x[j] gathers (layers.py:66-67, 210-211)
  */
 #ifndef PEMP_H_
 #define PEMP_H_
@@ -39,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PEMP_ABI_VERSION 21
+#define PEMP_ABI_VERSION 22
 
 enum {
   PEMP_OK = 0,
@@ -618,7 +621,8 @@ int pemp_mpn_status(const pemp_mpn_desc* desc, int64_t N, int64_t E, const void*
  * whose label contains `filter` ("*" = all, NULL or "" = off). pemp_prof_report synchronises those
  * events and writes "label count total_ms" lines into buf (returns the full length), then resets.
  * Labels: detect_nms, detect_top, detect_emit, pack_nodes, fully_graph, edge_features, knn_adj, knn_emit, score_graph,
- * mpn_prepare, node_embed, edge_embed, node_table, edge_step, edge_step_head, node_update, heads.
+ * mpn_prepare, node_embed, edge_embed, node_table, edge_step, edge_step_head, node_update, heads, seg_aggr_fwd,
+ * seg_aggr_bwd, seg_rows_sum.
  * "label@R": launch sites that are idempotent (the edge passes) issue their launch R times between
  * one event pair, so the per-launch average excludes the event-record overhead (count += R). */
 int pemp_prof_enable(const char* filter);
@@ -673,6 +677,50 @@ size_t pemp_label_edges_scratch_size(int B);
 int pemp_label_edges(const int64_t* edge_index, int64_t E, const int64_t* node_off, int B, int64_t N,
                      const int64_t* node_persons, const uint8_t* ambiguous, float* edge_labels, float* label_mask,
                      void* scratch, size_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Training-mode graph operators (mpn/train.py). fp32 rows of 64 floats (pemp_seg_rows_sum: 64 or 128), int32
+ * indices, no atomics, every output element written exactly once per call (callers never pre-zero), results
+ * bitwise identical from call to call. They consume a segment plan instead of edge_index:
+ *   perm_dst [E]      edge ids sorted by (dst, type[src], edge id)
+ *   seg_off [N T + 1] offsets into perm_dst; segment n T + t = the edges into node n from sources of type t
+ *   perm_src [E], src_off [N + 1]   edge ids sorted by (src, edge id) and their offsets
+ * Offsets are clamped into [0, E] and permutation entries outside [0, E) are skipped, never followed.
+ *
+ * pemp_seg_aggr_fwd: out[seg] over the segment's rows msgs[e], in list order (row groups of four combined in a
+ * fixed tree); an empty segment gives zeros for every kind.
+ *   PEMP_AGGR_ATTN  alpha_e = exp(s_e - max_seg) / (sum_seg exp(s - max_seg) + 1e-12), out = sum alpha_e msgs[e]
+ *                   (torch_scatter scatter_softmax, then scatter add); alpha[e] is stored when alpha != NULL
+ *   PEMP_AGGR_SUM / PEMP_AGGR_MEAN  sum, sum / max(count, 1)
+ *   PEMP_AGGR_MAX   per feature the maximum; arg[seg][f] (when arg != NULL) = the edge id of the first edge in
+ *                   segment order that attains it, -1 for an empty segment
+ * pemp_seg_aggr_bwd: grad_msgs[e] (every row once: each edge lies in one segment) and, for ATTN, grad_scores[e]
+ * (may be NULL) from grad_out [N T][64]:
+ *   ATTN  grad_msgs[e] = alpha_e g, grad_scores[e] = alpha_e (g . msgs[e] - g . out[seg]); exact with the 1e-12
+ *         term, the (below 1e-12 relative) gradient through the subtracted maximum is dropped. g . out[seg] is
+ *         evaluated as sum_k alpha_k (g . msgs[k]) / sum_k alpha_k over the segment (the same number up to the
+ *         1e-12 term, from the products the rows' own terms use, so that a segment's score gradients sum to zero
+ *         up to single roundings); `out` is not read and may be NULL
+ *   SUM   g;  MEAN  g / max(count, 1);  MAX  g[f] to row arg[seg][f], zero to the segment's other rows
+ *   needs msgs and alpha for ATTN and arg for MAX; the others may be NULL.
+ * pemp_seg_rows_sum: out[n] = sum of ga[e] over list a of n, then of gb[e] over list b of n (gb may be NULL), each
+ * in list order: the backward of the pair gather (x[dst], x[src]) with list a = (perm_dst, seg_off[::T]) and
+ * list b = (perm_src, src_off). W = 64 or 128 floats per row.
+ * Argument errors (unknown kind, T < 1, W, negative sizes, a required NULL pointer, ATTN without scores) are
+ * reported before the first HIP call. N == 0 returns 0 at once; E == 0 returns 0 without a launch, out zero-filled
+ * (arg -1).
+ * ---------------------------------------------------------------------------------------- */
+int pemp_seg_aggr_fwd(int kind, int T, int64_t N, int64_t E, const float* msgs /*[E][64]*/,
+                      const float* scores /*[E] or NULL*/, const int32_t* perm_dst, const int32_t* seg_off,
+                      float* out /*[N T][64]*/, float* alpha /*[E] or NULL*/, int32_t* arg /*[N T][64] or NULL*/,
+                      void* stream);
+int pemp_seg_aggr_bwd(int kind, int T, int64_t N, int64_t E, const float* grad_out /*[N T][64]*/, const float* msgs,
+                      const float* alpha, const float* out, const int32_t* arg, const int32_t* perm_dst,
+                      const int32_t* seg_off, float* grad_msgs /*[E][64]*/, float* grad_scores /*[E] or NULL*/,
+                      void* stream);
+int pemp_seg_rows_sum(int64_t N, int64_t E, int W, const float* ga /*[E][W]*/, const int32_t* perm_a,
+                      const int32_t* off_a /*[N + 1]*/, const float* gb /*[E][W] or NULL*/, const int32_t* perm_b,
+                      const int32_t* off_b, float* out /*[N][W]*/, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ import os
 
 LIB_PATH = os.environ.get("PEMP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc",
                                                      "libpemp.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 ERR_INVALID_ARG, ERR_HIP, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -3, -4
 BUILD_WRITE_COUNTS = 0x100          # pemp.h PEMP_BUILD_WRITE_COUNTS
@@ -147,6 +147,9 @@ SIGNATURES = {
                                   ctypes.c_double, ctypes.c_double, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pemp_label_edges_scratch_size": (c_sz, [c_i32]),
     "pemp_label_edges": (c_i32, [c_p, c_i64, c_p, c_i32, c_i64, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "pemp_seg_aggr_fwd": (c_i32, [c_i32, c_i32, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pemp_seg_aggr_bwd": (c_i32, [c_i32, c_i32, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pemp_seg_rows_sum": (c_i32, [c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 LABEL_OVERFLOW = 1                  # pemp.h PEMP_LABEL_OVERFLOW
 LABEL_CAND_DTYPE = [("g", "<i4"), ("n", "<u4"), ("sim", "<f8")]   # pemp.h pemp_label_cand

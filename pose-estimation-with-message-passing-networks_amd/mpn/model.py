@@ -5,7 +5,8 @@ identical and reference checkpoints load unchanged:
 ``mpn_node_cls.{mlp_edge,mlp_node,update_mlp,attn_net}``, ``edge_embedding``, ``node_embedding``,
 ``edge_classification``, ``node_classification``, ``classification``. The parameters are plain
 containers; ``forward`` folds them once per parameter version (eval-mode BatchNorm into the next
-Linear) and runs the whole network in ``pemp_mpn_forward`` (libpemp.so). Inference only.
+Linear) and runs the whole network in ``pemp_mpn_forward`` (libpemp.so). In training mode ``forward`` hands over
+to ``mpn/train.py`` (autograd over these layers and the segment kernels).
 """
 import ctypes
 import itertools
@@ -275,8 +276,9 @@ class NodeClassificationMPNSimple(nn.Module):
         return preds_edge, preds_node, preds_class, [None]
 
     def forward(self, x, edge_attr, edge_index, **kwargs):
-        if self.training:
-            raise NotImplementedError("pemp_amd MPN is inference-only: call .eval() (BatchNorm uses running stats)")
+        if self.training:    # autograd over the nn layers and the segment kernels of csrc/train.hip (mpn/train.py)
+            from .train import train_forward
+            return train_forward(self, x, edge_attr, edge_index, kwargs["node_types"])
         if x.device.type != "cuda":
             raise RuntimeError("pemp_amd MPN runs on the HIP device only (no CPU fallback)")
         L = _lib.lib()
