@@ -622,7 +622,11 @@ int pemp_mpn_status(const pemp_mpn_desc* desc, int64_t N, int64_t E, const void*
  * events and writes "label count total_ms" lines into buf (returns the full length), then resets.
  * Labels: detect_nms, detect_top, detect_emit, pack_nodes, fully_graph, edge_features, knn_adj, knn_emit, score_graph,
  * mpn_prepare, node_embed, edge_embed, node_table, edge_step, edge_step_head, node_update, heads, seg_aggr_fwd,
- * seg_aggr_bwd, seg_rows_sum.
+ * seg_aggr_bwd, seg_rows_sum. Model shapes off the published one report their fall-back kernels under labels of
+ * their own (the filter is a substring match, so "edge_embed" and "edge_step" still catch them): edge_embed_wide
+ * (an embedding layer or edge_attr_dim over 64: weights read from global memory), edge_embed_generic (the LDS
+ * embedding for a shape off the fixed A <= 32 -> 32 -> 64 -> 64 -> 64 layout), edge_step_head_generic (a recorded
+ * pass with an edge head other than 64 -> 64 -> 32 -> 1); `heads` marks node / class heads wider than 64.
  * "label@R": launch sites that are idempotent (the edge passes) issue their launch R times between
  * one event pair, so the per-launch average excludes the event-record overhead (count += R). */
 int pemp_prof_enable(const char* filter);

@@ -4092,7 +4092,12 @@ static int mpn_forward_impl(const pemp_mpn_desc* desc, const pemp_mpn_weights* w
   auto edge_embed = [&]() -> int {
   // (the range table is filled behind the edge order on the side stream, edge_prepare)
   if (E > 0 && steps >= 1) {
-    ProfScope prof("edge_embed", pst);
+    // (the label names the fall-backs apart: `wide` reads its weights from global memory, `generic` is the LDS
+    // kernel's runtime-shaped form for a shape off the fixed layout -- no precision has a straight-line kernel for it)
+    const bool emb_generic = emb_lds && !embed_fixed_shape(emb_prec == PEMP_PREC_FP32
+                                                               ? embed_layout(w->edge_emb, PEMP_PREC_F16X3)
+                                                               : emb_lo);
+    ProfScope prof(!emb_lds ? "edge_embed_wide" : emb_generic ? "edge_embed_generic" : "edge_embed", pst);
     if (emb_lds) {
       const int grid = (int)std::min<int64_t>((int64_t)(PEMP_EMBED_RESERVE ? edge_cus(E) : num_cus()) * EMB_PER_CU,
                                               (E + 16 * EMB_WAVES - 1) / (16 * EMB_WAVES));
@@ -4326,7 +4331,7 @@ static int mpn_forward_impl(const pemp_mpn_desc* desc, const pemp_mpn_weights* w
 #ifdef PEMP_STAMPS
       ea.stamps = it == g_diag_stamp_pass ? g_diag_stamps : nullptr;
 #endif
-      const char* label = record ? "edge_step_head" : "edge_step";
+      const char* label = !record ? "edge_step" : pub ? "edge_step_head" : "edge_step_head_generic";
       ProfScope prof(label, st);
       // a pass is idempotent (reads r_cur / NT / Q0, rewrites r_next / agg / logits), so the profiler
       // may repeat it between one event pair ("edge_step@R")
