@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PEMP_ABI_VERSION 22
+#define PEMP_ABI_VERSION 23
 
 enum {
   PEMP_OK = 0,
@@ -598,6 +598,16 @@ int pemp_mpn_forward_knn(const pemp_mpn_desc* desc, const pemp_mpn_weights* weig
 int pemp_mpn_prepare(const pemp_mpn_desc* desc, const int64_t* edge_index, const int64_t* node_types, int64_t N,
                      int64_t E, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Where the type-major edge order lies inside a workspace of pemp_mpn_workspace_size(desc, N, E) bytes (host
+ * arithmetic, no device call; no reference counterpart: for tests and tools that read the order back). Byte
+ * offsets, every array int32: offs[0] seg [num_types N + 1] (segment (t, d) = [seg[t N + d], seg[t N + d + 1]):
+ * the edges into d from sources of type t, in edge-id order; seg[num_types N] = the valid edge total), offs[1]
+ * wg_start [18] (the edge passes' workgroup split over the types), offs[2] s_src [E], offs[3] s_dst [E], offs[4]
+ * s_orig [E] (source, target and edge id of the edge at each sorted position). pemp_mpn_prepare and every
+ * pemp_mpn_forward* write them. After a forward with steps >= 1, s_dst carries the edge passes' packed segment
+ * positions in its high byte (edge_ranges_kernel writes them): the target is its low 24 bits. */
+int pemp_mpn_order_layout(const pemp_mpn_desc* desc, int64_t N, int64_t E, size_t offs[5]);
+
 /* The node embedding / node head / class head weights in the node kernels' LDS layout, built once
  * per weight set (stream-ordered) instead of once per forward: image of
  * pemp_mpn_node_image_floats(weights) floats, then weights->node_img = image. */
@@ -621,7 +631,8 @@ int pemp_mpn_status(const pemp_mpn_desc* desc, int64_t N, int64_t E, const void*
  * whose label contains `filter` ("*" = all, NULL or "" = off). pemp_prof_report synchronises those
  * events and writes "label count total_ms" lines into buf (returns the full length), then resets.
  * Labels: detect_nms, detect_top, detect_emit, pack_nodes, fully_graph, edge_features, knn_adj, knn_emit, score_graph,
- * mpn_prepare, node_embed, edge_embed, node_table, edge_step, edge_step_head, node_update, heads, seg_aggr_fwd,
+ * mpn_prepare (the sorting prepare; the closed forms report under mpn_prepare_fully, mpn_prepare_sym and
+ * mpn_prepare_knn, so the filter "mpn_prepare" catches all four), node_embed, edge_embed, node_table, edge_step, edge_step_head, node_update, heads, seg_aggr_fwd,
  * seg_aggr_bwd, seg_rows_sum. Model shapes off the published one report their fall-back kernels under labels of
  * their own (the filter is a substring match, so "edge_embed" and "edge_step" still catch them): edge_embed_wide
  * (an embedding layer or edge_attr_dim over 64: weights read from global memory), edge_embed_generic (the LDS

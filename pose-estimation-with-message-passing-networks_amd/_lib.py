@@ -9,7 +9,7 @@ import os
 
 LIB_PATH = os.environ.get("PEMP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc",
                                                      "libpemp.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 ERR_INVALID_ARG, ERR_HIP, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -3, -4
 BUILD_WRITE_COUNTS = 0x100          # pemp.h PEMP_BUILD_WRITE_COUNTS
@@ -118,6 +118,7 @@ SIGNATURES = {
                                      c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_sz,
                                      c_p]),
     "pemp_mpn_prepare": (c_i32, [ctypes.POINTER(PempMpnDesc), c_p, c_p, c_i64, c_i64, c_p, c_sz, c_p]),
+    "pemp_mpn_order_layout": (c_i32, [ctypes.POINTER(PempMpnDesc), c_i64, c_i64, c_p]),
     "pemp_mpn_edge_image_floats": (c_sz, [ctypes.POINTER(PempMpnDesc), ctypes.POINTER(PempMpnWeights)]),
     "pemp_mpn_edge_image": (c_i32, [ctypes.POINTER(PempMpnDesc), ctypes.POINTER(PempMpnWeights), c_p, c_sz, c_p]),
     "pemp_mpn_node_image_floats": (c_sz, [ctypes.POINTER(PempMpnWeights)]),

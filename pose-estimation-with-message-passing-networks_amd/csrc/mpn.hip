@@ -252,19 +252,27 @@ struct MpnWs {
 constexpr int IMG_FLOATS = 112 * 1024;  // >= LDS image of a node embedding (<= 4 layers, <= 128 wide) + both heads (<= 64 wide)
 constexpr int EIMG_MAX_STRIDE = 4 * D * LDW + (2 * D + 4) + (D + 32) * LDW + D + 32 + 32 + 4;   // edge image floats per type (max)
 
-static MpnWs mpn_carve(void* base, int T, int64_t N, int64_t E, size_t* bytes) {
+// order_offs (pemp_mpn_order_layout): the byte offsets of seg, wg_start, s_src, s_dst and s_orig
+static MpnWs mpn_carve(void* base, int T, int64_t N, int64_t E, size_t* bytes, size_t* order_offs = nullptr) {
   Carver c(base);
   MpnWs w;
+  size_t oo[5];
   const int64_t K = (int64_t)T * N;
   w.err = c.take<int>(64);               // err[0..3] then cnt: zeroed together
   w.cnt = w.err + 64;
   c.take<int>(K + 1);
   w.seg = c.take<int>(K + 1);
+  oo[0] = c.last;
   w.wg_start = c.take<int>(MAXT + 2);
+  oo[1] = c.last;
   w.perm = c.take<int>(E);
   w.s_src = c.take<int>(E);
+  oo[2] = c.last;
   w.s_dst = c.take<int>(E);
+  oo[3] = c.last;
   w.s_orig = c.take<int>(E);
+  oo[4] = c.last;
+  if (order_offs) std::copy(oo, oo + 5, order_offs);
   w.X = c.take<float>(N * 128);
   w.NT = c.take<float>(N * (128 + 64 * (int64_t)T));
   w.agg = c.take<float>(N * T * D);
@@ -3224,7 +3232,7 @@ __global__ __launch_bounds__(256) void fully_prepare_kernel(FullyPrepArgs a) {
         const int mid = (lo + hi + 1) >> 1;
         if (noff[mid] <= n) lo = mid; else hi = mid - 1;
       }
-      const int64_t t = tv[k];
+      const int64_t t = T == 1 ? 0 : tv[k];          // one message MLP ignores the types, like mpn_count_kernel
       if (t >= 0 && t < T) atomicAdd(&cnt_bt[lo][t], 1);
       else bad_sh = 1;                               // skipped as a source, like mpn_count_kernel
     }
@@ -3244,7 +3252,7 @@ __global__ __launch_bounds__(256) void fully_prepare_kernel(FullyPrepArgs a) {
   }
   const int ob = noff[b], nb = noff[b + 1] - noff[b];
   for (int i = threadIdx.x; i < nb; i += 256) {
-    const int64_t t = a.types[(int64_t)(ob + i) * a.ts];
+    const int64_t t = T == 1 ? 0 : a.types[(int64_t)(ob + i) * a.ts];
     lty[i] = (t >= 0 && t < T) ? (int)t : -1;
   }
   __syncthreads();
@@ -3590,6 +3598,7 @@ __global__ __launch_bounds__(1024) void knn_prepare_kernel(KnnPrepArgs a) {
     for (int w = 0; w < KP_W; ++w) rr[i][w] = a.R[(int64_t)d * KP_W + w];
     tr[i] = a.types[(int64_t)d * a.ts];
   }
+  if (T == 1) tr[0] = tr[1] = 0;                     // one message MLP ignores the types, like mpn_count_kernel
   if (tid <= B) noff[tid] = no;
   if (wave == 1) {                                   // edge id base of every image (B <= 64)
     const int e = lane < B ? ec : 0;
@@ -3619,7 +3628,7 @@ __global__ __launch_bounds__(1024) void knn_prepare_kernel(KnnPrepArgs a) {
 #pragma unroll
   for (int i = 0; i < 2; ++i)
     if (tid + 1024 * i < N) mark(tid + 1024 * i, tr[i]);
-  for (int d = tid + 2048; d < N; d += 1024) mark(d, a.types[(int64_t)d * a.ts]);
+  for (int d = tid + 2048; d < N; d += 1024) mark(d, T == 1 ? 0 : a.types[(int64_t)d * a.ts]);
   if (__ballot(bad) && lane == 0) bad_sh = 1;
   __syncthreads();
   KP_CLK(2);
@@ -3645,7 +3654,7 @@ __global__ __launch_bounds__(1024) void knn_prepare_kernel(KnnPrepArgs a) {
     unsigned long long v[KP_W];
 #pragma unroll
     for (int w = 0; w < KP_W; ++w) v[w] = a.R[(int64_t)d * KP_W + w];
-    row(d, v, a.types[(int64_t)d * a.ts]);
+    row(d, v, T == 1 ? 0 : a.types[(int64_t)d * a.ts]);
   }
   __syncthreads();
   KP_CLK(3);
@@ -3829,7 +3838,7 @@ static int launch_prepare_sym(const pemp_mpn_desc* desc, const int64_t* edge_ind
   const int T = desc->num_types;
   const int64_t tstride = desc->types_stride > 0 ? desc->types_stride : 1;
   const int64_t K = (int64_t)T * N;
-  ProfScope prof("mpn_prepare", st);
+  ProfScope prof("mpn_prepare_sym", st);
   int2* rows = reinterpret_cast<int2*>(ws.sym);
   int* flags = ws.sym + 2 * N;
   unsigned* packed = reinterpret_cast<unsigned*>(ws.perm);
@@ -4048,7 +4057,7 @@ static int mpn_forward_impl(const pemp_mpn_desc* desc, const pemp_mpn_weights* w
       // vs 15 us at C3)
       const unsigned gx =
           (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)T * fully_nmax * FULLY_PARTS + 511) / 512));
-      ProfScope prof("mpn_prepare", pst);
+      ProfScope prof("mpn_prepare_fully", pst);
       hipLaunchKernelGGL(fully_prepare_kernel, dim3(gx, (unsigned)fully_B), dim3(256), 0, pst, fa);
       PEMP_LAUNCH_CHECK();
     } else if (knn && N > 0) {
@@ -4065,7 +4074,7 @@ static int mpn_forward_impl(const pemp_mpn_desc* desc, const pemp_mpn_weights* w
       ka.s_dst = ws.s_dst;
       ka.s_orig = ws.s_orig;
       ka.err = ws.err;
-      ProfScope prof("mpn_prepare", pst);
+      ProfScope prof("mpn_prepare_knn", pst);
       hipLaunchKernelGGL(knn_prepare_kernel, dim3((unsigned)T, (unsigned)((N + KP_CH - 1) / KP_CH)), dim3(1024), 0, pst,
                          ka);
       PEMP_LAUNCH_CHECK();
@@ -4642,6 +4651,13 @@ extern "C" int pemp_mpn_prepare(const pemp_mpn_desc* desc, const int64_t* edge_i
   if (N == 0) return PEMP_OK;
   return launch_prepare(desc, edge_index, node_types, N, E, mpn_carve(workspace, desc->num_types, N, E, nullptr),
                         as_stream(stream));
+}
+
+extern "C" int pemp_mpn_order_layout(const pemp_mpn_desc* desc, int64_t N, int64_t E, size_t* offs) {
+  PEMP_CHECK_ARG(desc && offs && desc->num_types >= 1 && desc->num_types <= MAXT, "pemp_mpn_order_layout: bad desc");
+  PEMP_CHECK_ARG(N >= 0 && E >= 0, "pemp_mpn_order_layout: N=%lld E=%lld out of range", (long long)N, (long long)E);
+  mpn_carve(nullptr, desc->num_types, N, E, nullptr, offs);
+  return PEMP_OK;
 }
 
 extern "C" size_t pemp_mpn_edge_image_floats(const pemp_mpn_desc* desc, const pemp_mpn_weights* w) {

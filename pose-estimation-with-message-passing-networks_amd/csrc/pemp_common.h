@@ -102,10 +102,12 @@ static inline int num_cus() {
 struct Carver {
   char* base;
   size_t used;
-  explicit Carver(void* b) : base(static_cast<char*>(b)), used(0) {}
+  size_t last;   // byte offset of the slice handed out last
+  explicit Carver(void* b) : base(static_cast<char*>(b)), used(0), last(0) {}
   template <typename T>
   T* take(size_t count) {
     used = align_up(used, 256);
+    last = used;
     T* p = reinterpret_cast<T*>(base ? base + used : nullptr);
     used += count * sizeof(T);
     return p;

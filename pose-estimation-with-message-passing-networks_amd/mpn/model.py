@@ -362,6 +362,13 @@ class NodeClassificationMPNSimple(nn.Module):
         return preds_edge, preds_node, preds_class, [None]
 
 
+    def _order_workspace(self, N, E):
+        """(descriptor, workspace) of the last forward over N nodes and E edges on the current stream: tests read the
+        edge order back from it (pemp_mpn_order_layout)."""
+        dev = next(self.parameters()).device
+        return self._desc_ref, self._ws.get(_lib.lib().pemp_mpn_workspace_size(self._desc_ref, N, E), dev)
+
+
     # ---- capacity mode (graph_constructor.bind_mpn): the forward queued before the detection counts are known ----
     def _forward_cap(self, x, edge_attr, joint_det, n_cap, e_cap, n_det, det_cap, node_off, B, counts_in_off=False):
         """Queue pemp_mpn_forward_fully_cap on the capacity buffers of pemp_fully_graph_build_cap (x [n_cap, C],
