@@ -455,8 +455,17 @@ typedef struct pemp_mpn_desc {
  * pemp_fully_graph_build_cap wrote them with PEMP_BUILD_WRITE_COUNTS: the forward reads them instead of deriving
  * them from n_det in a launch of its own */
 #define PEMP_MPN_COUNTS_IN_OFFSETS 2
+/* The edge embedding and the first pass always as two launches. Without it the published composed f16x3 attention
+ * model (steps >= 2, first pass not recorded, prebuilt edge_img) runs them as one; the logits are the same bits
+ * either way. For A/B runs and tests. */
+#define PEMP_MPN_TWO_LAUNCH_FIRST 4
+/* While the library profiler (pemp_prof_enable) records, a forward keeps the two launches and their labels
+ * (edge_embed, edge_step); with this flag it runs the fused pass there too (label edge_first). */
+#define PEMP_MPN_FUSED_FIRST_PROFILED 8
 
 size_t pemp_mpn_workspace_size(const pemp_mpn_desc* desc, int64_t N, int64_t E);
+/* LDS bytes of one workgroup of the fused first pass (one workgroup per CU: at most 160 KiB) */
+size_t pemp_mpn_fused_first_lds_bytes(void);
 /* x [N,node_in_dim], edge_attr [E,edge_attr_dim], edge_index [2,E] (row 0 source j, row 1
  * target i), node_types [N] with element stride desc->types_stride (already mapped by
  * sum_node_types; values < T).

@@ -796,17 +796,19 @@ struct EmbedLayout {
 
 // interleaved bf16 row [hi in_pad | lo in_pad | pad 16] (elements): in_pad + 8 dwords, = 8 * odd
 // (mod 64) for in_pad = 32 kb, which keeps the ds_read_b128 fragment reads conflict free
-static int lds_stride_bf(int in_pad) { return 2 * in_pad + 16; }
+__host__ __device__ constexpr int lds_stride_bf(int in_pad) { return 2 * in_pad + 16; }
 
-static EmbedLayout embed_layout(const pemp_mlp& m, int prec) {
+// (from the layers' dimensions: a constant expression for the published shape, embed_layout_published)
+__host__ __device__ constexpr EmbedLayout embed_layout_dims(int n, const int* in_dim, const int* out_dim, const int* relu,
+                                                            int prec) {
   EmbedLayout L{};
-  L.n = m.n_layers;
+  L.n = n;
   L.prec = prec;
   int off = 0, goff = 0;
   for (int l = 0; l <= L.n; ++l) {
-    const int in = l < L.n ? m.layer[l].in_dim : 64, out = l < L.n ? m.layer[l].out_dim : 64;
+    const int in = l < L.n ? in_dim[l] : 64, out = l < L.n ? out_dim[l] : 64;
     L.ob[l] = (out + 15) / 16;
-    L.relu[l] = l < L.n ? m.layer[l].relu : 0;
+    L.relu[l] = l < L.n ? relu[l] : 0;
     L.w_off[l] = off;
     if (prec != PEMP_PREC_FP32) {
       L.kb[l] = (in + 31) / 32;
@@ -826,6 +828,24 @@ static EmbedLayout embed_layout(const pemp_mlp& m, int prec) {
   }
   L.total = off;
   return L;
+}
+
+static EmbedLayout embed_layout(const pemp_mlp& m, int prec) {
+  int in[4] = {}, out[4] = {}, relu[4] = {};
+  const int n = m.n_layers < 4 ? m.n_layers : 4;   // (mlp_ok: <= 4 layers)
+  for (int l = 0; l < n; ++l) {
+    in[l] = m.layer[l].in_dim;
+    out[l] = m.layer[l].out_dim;
+    relu[l] = m.layer[l].relu;
+  }
+  return embed_layout_dims(n, in, out, relu, prec);
+}
+
+// the split-precision layout of the published embedding (A <= 32 -> 32 -> 64 -> 64 -> 64): what embed_layout gives for
+// every model that passes embed_fixed_shape, known at compile time (the fused first pass, edge_step_kernel STAGE_FIRST)
+__host__ __device__ constexpr EmbedLayout embed_layout_published() {
+  constexpr int in[4] = {32, 32, 64, 64}, out[4] = {32, 64, 64, 64}, relu[4] = {1, 1, 1, 0};
+  return embed_layout_dims(4, in, out, relu, PEMP_PREC_F16X3);
 }
 
 // One Linear (+ReLU) on fragments, weights and bias in LDS, runtime block counts <= 4.
@@ -951,17 +971,16 @@ __device__ __forceinline__ void load_edge_attr(rsrc_t rs_ea, int A, int o, float
 }
 
 // the first 32 features of the tile's edge_attr rows (A <= 32: the fixed published shape), raw and unmasked,
-// issued one tile ahead of their use (ea_mask)
-__device__ __forceinline__ void load_edge_attr32(rsrc_t rs_ea, int A, int o, float (&v)[2][4]) {
-  const int g = __lane_id() >> 4;
+// issued one tile ahead of their use (ea_mask). g: the lane's row group (a caller inside a register-tight loop passes
+// it re-derived per trip, so that the eight column terms are recomputed instead of kept live or spilled)
+__device__ __forceinline__ void load_edge_attr32(rsrc_t rs_ea, int A, int o, float (&v)[2][4], int g = __lane_id() >> 4) {
   const int row = o * A * 4;
 #pragma unroll
   for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
     for (int r = 0; r < 4; ++r) v[mb][r] = __int_as_float(bld1(rs_ea, row + 4 * min(16 * mb + 4 * g + r, A - 1)));
 }
-__device__ __forceinline__ void ea_mask(int A, const float (&v)[2][4], float (&x)[4][4]) {
-  const int g = __lane_id() >> 4;
+__device__ __forceinline__ void ea_mask(int A, const float (&v)[2][4], float (&x)[4][4], int g = __lane_id() >> 4) {
 #pragma unroll
   for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
@@ -1284,7 +1303,7 @@ __global__ __launch_bounds__(256) void embed_image_kernel(pemp_mlp emb, EmbedLay
                            e1_bf, comp_bf, comp_b);
 }
 // floats of the composed image the kernel copies (no W1_e_cur tile)
-__host__ __device__ inline int embed_comp_floats(const EmbedLayout& Lo) { return (Lo.total + 3) & ~3; }
+__host__ __device__ constexpr int embed_comp_floats(const EmbedLayout& Lo) { return (Lo.total + 3) & ~3; }
 
 __device__ inline void dma_to_lds(float* __restrict__ lds, const float* __restrict__ src, int n);
 __device__ __forceinline__ void lds_drain();
@@ -1409,6 +1428,11 @@ struct EdgeStepArgs {
   unsigned long long* stamps;   // diagnostic builds (-DPEMP_STAMPS) only: per-wave phase timestamps
   const int64_t* ne;            // capacity mode: device-side (N, E); N / E above are then the capacities
   int rec;                      // capacity mode: edge_logits is the base, the pass writes row rec (of E)
+  // fused first pass (STAGE_FIRST): the edge_attr rows [E][A] and the composed embedding's prebuilt LDS image; the pass
+  // computes R0 in registers instead of reading r_cur and writes the Q0 rows
+  const float* ea;
+  int A;
+  const float* emb_img;
 };
 
 // Diagnostic phase timestamps (-DPEMP_STAMPS builds only; tools/edge_timeline.py): lane 0 of each
@@ -1580,6 +1604,13 @@ constexpr int IMG_VEC = 2 * D + 4;
 constexpr int IMG_HEAD = (D + 32) * LDW + D + 32 + 32 + 4;
 __host__ __device__ constexpr int img_common(int upd) { return (3 + upd) * D * LDW + IMG_VEC; }
 __host__ __device__ constexpr int img_stride(int upd, int head) { return img_common(upd) + (head ? IMG_HEAD : 0); }
+// floats of one wave's piece record (edge_step_kernel: raw aggregate, running max, normaliser, pad)
+constexpr int EDGE_PIECE_F = 68;
+// static LDS of the fused first pass (edge_step_kernel STAGE_FIRST): the pass image, the composed embedding image in
+// place of the row buffers, and the piece records
+__host__ __device__ constexpr size_t edge_first_lds_bytes() {
+  return (size_t)(img_common(1) + embed_comp_floats(embed_layout_published()) + 16 * 2 * EDGE_PIECE_F) * sizeof(float);
+}
 
 struct EdgeImgArgs {
   int T, prec, upd, head, aggr;
@@ -1656,7 +1687,12 @@ __global__ __launch_bounds__(256) void edge_image_kernel(EdgeImgArgs a) {
 // while tile k computes; Q0 rows and the node-table gathers of tile k are issued before that DMA,
 // so waiting for them never waits for it; the indices run two tiles ahead.
 // PREC: 0 = exact fp32 MFMA (v_mfma_f32_16x16x4_f32), 1 = bf16x3, 2 = f16x3 (gemm_bf3 / gemm_h3).
-enum { STAGE_MID = 1, STAGE_LAST = 2, STAGE_EPT = 4 };
+// STAGE_FIRST (with STAGE_MID; f16x3, attention, UPD, no head, the composed published embedding): the first pass with
+// the edge embedding fused in. Per tile it runs edge_embed_kernel<2, 2>'s arithmetic on the tile's edge_attr rows --
+// the same device functions in the same order, so Q0 and R0 have the same bits -- uses R0 as the tile's r, stores Q0
+// for the later passes and keeps it in registers for its own r_next. R0 never reaches memory. No LDS-DMA row buffer:
+// its LDS holds the composed embedding image instead, and every memory wait is the compiler's.
+enum { STAGE_MID = 1, STAGE_LAST = 2, STAGE_EPT = 4, STAGE_FIRST = 8 };
 
 // waves per workgroup (one workgroup per CU): 16 (<= 128 VGPRs); a recorded pass carries the head
 // weights in LDS and needs more registers: 12
@@ -1817,6 +1853,11 @@ __device__ __forceinline__ float pemp_exp(float x) { return PEMP_FAST_EXP ? __ex
 #endif
 // segment normaliser: IEEE division or v_rcp_f32 (1 ulp)
 __device__ __forceinline__ float pemp_rcp(float x) { return PEMP_FAST_RCP ? __builtin_amdgcn_rcpf(x) : 1.0f / x; }
+// the fused first pass (STAGE_FIRST): Q0 kept in registers from the embedding to the r_next GEMM (0) or read back by
+// the wave that stored it (1, the default: DESIGN §4)
+#ifndef PEMP_FIRST_Q0_RELOAD
+#define PEMP_FIRST_Q0_RELOAD 1
+#endif
 #ifndef PEMP_XCD_MAP
 #define PEMP_XCD_MAP 1
 #endif
@@ -1834,11 +1875,18 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
   // the last pass writes no next r: its copy of the image starts past W1 (SKIP floats)
   constexpr int SKIP = MID ? 0 : D * LDW;
   constexpr int IMG_F = img_common(UPD) + (HEAD == 1 ? IMG_HEAD : 0) - SKIP;
+  constexpr bool FIRST = (STAGE & STAGE_FIRST) != 0;
+  static_assert(!FIRST || (MID && !EPT && HEAD == 0 && PREC == 2 && UPD == 1 && AGG == PEMP_AGGR_ATTN),
+                "the fused first pass is built for the published composed shape only");
+  constexpr EmbedLayout ELO = embed_layout_published();
+  constexpr int EMB_F = embed_comp_floats(ELO);
   __shared__ __attribute__((aligned(16))) float img[IMG_F];
-  __shared__ __attribute__((aligned(16))) float rbuf[NW * 1024];
+  // the waves' 4 KB row buffers; FIRST: the composed embedding image (no rows are read)
+  __shared__ __attribute__((aligned(16))) float rbuf[FIRST ? EMB_F : NW * 1024];
   // per wave: the pieces of the segments cut by its range ends ([0] the first segment, begun by an earlier wave;
   // [1] the last, continued by later waves): raw aggregate (64 floats), running max, normaliser
-  constexpr int PREC_F = 68;
+  constexpr int PREC_F = EDGE_PIECE_F;
+  static_assert(!FIRST || (NW == 16 && edge_first_lds_bytes() <= 160 * 1024), "the fused first pass's LDS");
   __shared__ __attribute__((aligned(16))) float pieces[NW * 2 * PREC_F];
   float* vec = img + (3 + UPD) * D * LDW - SKIP;   // e2_b[64] | attn_w[64] | attn_b
   float* hw = img + img_common(UPD) - SKIP;        // HEAD 1: L1 [64][LDW], L2 [32][LDW], b1[64], b2[32], w3[32], b3
@@ -1875,6 +1923,7 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
   const rsrc_t rs_dst = make_rsrc(a.s_dst, E * 4), rs_src = make_rsrc(a.s_src, E * 4);
   const rsrc_t rs_nt = make_rsrc(a.NT, (int)a.N * a.t_nt_ld * 4);
   const rsrc_t rs_orig = make_rsrc(a.s_orig, E * 4);
+  const rsrc_t rs_ea = make_rsrc(a.ea, FIRST ? E * a.A * 4 : 0);   // (32-bit: the host keeps E * A * 4 < 2^31)
   const int nt_row = a.t_nt_ld * 4;                  // bytes per node-table row
   const int nt_p = (128 + 64 * t) * 4;               // byte offset of P_t in a row (SGPR soffset)
   // a tile's gathers, issued at the end of the previous tile (the first tile's while the weight image is
@@ -1890,6 +1939,20 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
       xp[ob] = bld4(rs_nt, va + 64 * ob, nt_p);
     }
   };
+  // FIRST: the same gathers in two parts, each issued inside the tile where its registers come free
+  auto gather_ab = [&](int dstv, int srcv) {
+    const int va = sdst_id(dstv) * nt_row + 16 * g, vb = srcv * nt_row + 256 + 16 * g;
+#pragma unroll
+    for (int ob = 0; ob < 4; ++ob) {
+      xa[ob] = bld4(rs_nt, va + 64 * ob);
+      xb[ob] = bld4(rs_nt, vb + 64 * ob);
+    }
+  };
+  auto gather_p = [&](int dstv) {
+    const int va = sdst_id(dstv) * nt_row + 16 * g;
+#pragma unroll
+    for (int ob = 0; ob < 4; ++ob) xp[ob] = bld4(rs_nt, va + 64 * ob, nt_p);
+  };
   // prologue order: the first two tiles' indices (the only loads the first gathers wait for: small, ahead of the
   // kernel-start burst), the type image, the first tile's node-table gathers, then its r rows
   int dst_n = 0, src_n = 0, dst_nn = 0, src_nn = 0;
@@ -1899,6 +1962,10 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
     dst_nn = bld1(rs_dst, 4 * min(first + 16 + c, end - 1));
     src_nn = bld1(rs_src, 4 * min(first + 16 + c, end - 1));
   }
+  // FIRST: original ids two tiles ahead and the edge_attr rows one tile ahead, as edge_embed_kernel reads them
+  int o_next = 0;
+  float ea_n[2][4];
+  if (FIRST && first < end) o_next = bld1(rs_orig, 4 * min(first + c, end - 1));
   {
     // the block's type image: IMG_F floats, 1 KB per wave instruction, waves interleaved
     const float* src = a.img + (int64_t)t * a.img_stride + SKIP;
@@ -1907,8 +1974,20 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
       dma16(src + 256 * k + 4 * lane, img + 256 * k);
     if (TAIL && wave == NW - 1 && 4 * lane < TAIL)
       *reinterpret_cast<float4*>(&img[256 * PIECES + 4 * lane]) = ld4(src + 256 * PIECES + 4 * lane);
+    if constexpr (FIRST) {   // then the composed embedding image (a multiple of 4 floats)
+      constexpr int EP = EMB_F / 256, ET = EMB_F - EP * 256;
+      for (int k = wave; k < EP; k += NW) dma16(a.emb_img + 256 * k + 4 * lane, rbuf + 256 * k);
+      if (ET && wave == NW - 2 && 4 * lane < ET)
+        *reinterpret_cast<float4*>(&rbuf[256 * EP + 4 * lane]) = ld4(a.emb_img + 256 * EP + 4 * lane);
+    }
   }
-  if (first < end) {
+  if (FIRST) {
+    // (the tile's node-table gathers are issued inside the tile, behind the embedding layers)
+    if (first < end) {
+      load_edge_attr32(rs_ea, a.A, o_next, ea_n);
+      o_next = bld1(rs_orig, 4 * min(first + 16 + c, end - 1));
+    }
+  } else if (first < end) {
     gather_nt(dst_n, src_n, true);
     dma_rows(rs_r, first, mybuf, lane);
     if (HEAD == 1) orig_t = bld1(rs_orig, 4 * min(first + c, end - 1));
@@ -1922,6 +2001,7 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
   const rsrc_t rs_agg = make_rsrc(a.agg, (int)a.N * T * 256);
   const u32x4v_s rw_r = rsrc_words(a.r_cur, end * 256);
   const u32x4v_s rw_q = rsrc_words(a.Q0, end * 256);
+  const rsrc_t rs_q0 = make_rsrc(a.Q0, FIRST ? E * 256 : 0);   // FIRST: the Q0 rows are written here
   // stores issued after a tile's DMA, all unconditional (masked lanes write past the buffer end): the
   // r_next rows (middle passes that write them) and the aggregate rows
   const bool store_next = MID && a.write_next;
@@ -1960,15 +2040,38 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
     // this tile's rows (DMA issued one tile ago) have landed: the ops issued after that DMA are the
     // previous tile's unconditional stores and this tile's gathers
     constexpr int NG = 12 + (HEAD == 1 ? 1 : 0);
-    if (tile_no > 0) {
+    if (!FIRST && tile_no > 0) {
       if (store_next) dma_wait<8 + NG>();
       else dma_wait<4 + NG>();
     }
-    // this tile's r rows from the DMA buffer (row c, chunk (4 ob + g) ^ 4 (c & 3)); the lane terms are
-    // re-derived from the opaque zero each tile (kept live across the loop they would be spilled)
     float h[4][4], m[4][4], q0r[4][4];
     float4 rr[4];
-    {
+    if constexpr (FIRST) {
+      // the tile's embedding (edge_embed_kernel's composed body): q0r = Q0, stored for the later passes and kept for
+      // this pass's r_next; rr = R0 = W_r h3 + b_r on its own accumulator
+      const float* smz = rbuf + z;
+      float y[4][4], r0[4][4];
+      Frag<PREC> fx;
+      ea_mask(a.A, ea_n, q0r, g + z);
+      load_edge_attr32(rs_ea, a.A, o_next, ea_n, g + z);   // the next tile's rows (clamped ids past the range: harmless)
+      o_next = bld1(rs_orig, 4 * min(base + 32 + c, end - 1));
+      embed_tile_fixed<PREC, true>(smz, ELO, q0r, y, fx);   // q0r = Q0 (domain), y = h3, fx = h3's split
+      const int vq0 = valid ? p * 256 + 16 * g : OOB_VOFF;   // masked lanes: stores dropped
+#pragma unroll
+      for (int ob = 0; ob < 4; ++ob) bst4(rs_q0, vq0 + 64 * ob, q0r[ob][0], q0r[ob][1], q0r[ob][2], q0r[ob][3]);
+      gather_ab(dst, src);                          // this tile's A / B node-table rows, in flight over the R0 GEMM
+      const float* br = smz + ELO.b_off[4];
+#pragma unroll
+      for (int ob = 0; ob < 4; ++ob) {
+        const float4 bb = ld4(br + 16 * ob + 4 * g);
+        r0[ob][0] = bb.x; r0[ob][1] = bb.y; r0[ob][2] = bb.z; r0[ob][3] = bb.w;
+      }
+      gemm_f<PREC, 4>(smz + ELO.w_off[4], y, fx, r0);
+#pragma unroll
+      for (int ob = 0; ob < 4; ++ob) rr[ob] = make_float4(r0[ob][0], r0[ob][1], r0[ob][2], r0[ob][3]);
+    } else {
+      // this tile's r rows from the DMA buffer (row c, chunk (4 ob + g) ^ 4 (c & 3)); the lane terms are
+      // re-derived from the opaque zero each tile (kept live across the loop they would be spilled)
       const int cz = c + z, rowb = 64 * cz + 4 * g;
 #pragma unroll
       for (int ob = 0; ob < 4; ++ob) rr[ob] = ld4(mybuf + (rowb ^ (16 * (ob ^ (cz & 3)))));
@@ -1978,7 +2081,7 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
     // Q0 rows of this tile go by LDS-DMA into the buffer just read, overlapping the first half of the tile
     const int vq = p * 256 + 16 * g;
     const int orig = orig_t;
-    if (MID) {
+    if (MID && !FIRST) {
 #pragma unroll
       for (int ob = 0; ob < 4; ++ob) asm volatile("" ::"v"(xa[ob].x), "v"(xb[ob].x), "v"(xp[ob].x));
       if (store_next) dma_rows_async(rw_q, base, mybuf, lane);
@@ -1999,6 +2102,20 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
         h[ob][0] = rr[ob].x + xa[ob].x + xb[ob].x; h[ob][1] = rr[ob].y + xa[ob].y + xb[ob].y;
         h[ob][2] = rr[ob].z + xa[ob].z + xb[ob].z; h[ob][3] = rr[ob].w + xa[ob].w + xb[ob].w;
       }
+    }
+    if constexpr (FIRST) {
+      // the P_t rows (read at the message GEMM) and, with PEMP_FIRST_Q0_RELOAD, this wave's own Q0 rows back through
+      // the descriptor they were stored with (read at the r_next GEMM): issued once the A / B rows are consumed
+#pragma unroll
+      for (int ob = 0; ob < 4; ++ob) asm volatile("" ::"v"(h[ob][0]), "v"(h[ob][1]), "v"(h[ob][2]), "v"(h[ob][3]));
+      gather_p(dst);
+#if PEMP_FIRST_Q0_RELOAD
+#pragma unroll
+      for (int ob = 0; ob < 4; ++ob) {
+        const float4 q = bld4(rs_q0, min(p, end - 1) * 256 + 16 * g + 64 * ob);
+        q0r[ob][0] = q.x; q0r[ob][1] = q.y; q0r[ob][2] = q.z; q0r[ob][3] = q.w;
+      }
+#endif
     }
     // other passes: the r rows of tile k+1 into the buffer this tile's rows were read from, once every
     // gather of this tile has returned (the compiler's waits on those would otherwise also wait on the DMA)
@@ -2071,7 +2188,7 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
     }
     Frag<PREC> fe;                                // e' split once for the r_next, head and message GEMMs
     prep<PREC, true>(ep, fe);
-    if (MID) {
+    if (MID && !FIRST) {
       // this tile's Q0 rows have landed (only the two index loads were issued after their DMA): read them,
       // then the r rows of tile k+1 into the same buffer
       if (store_next) {
@@ -2190,7 +2307,7 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
 #if PEMP_GATHER_FIRST
     // the next tile's gathers ahead of this tile's aggregate stores: waiting for them at the next tile then does
     // not wait for those stores too (vmcnt retires in issue order)
-    gather_nt(dst_n, src_n, more);
+    if (!FIRST) gather_nt(dst_n, src_n, more);
     if (HEAD == 1) orig_t = bld1(rs_orig, 4 * min(p + 16, end - 1));
 #endif
     {
@@ -2216,7 +2333,7 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
     }
 #if !PEMP_GATHER_FIRST
     {   // the next tile's gathers, unconditional (past the range: OOB offsets, no traffic)
-      gather_nt(dst_n, src_n, more);
+      if (!FIRST) gather_nt(dst_n, src_n, more);
       if (HEAD == 1) orig_t = bld1(rs_orig, 4 * min(p + 16, end - 1));
     }
 #endif
@@ -4098,7 +4215,19 @@ static int mpn_forward_impl(const pemp_mpn_desc* desc, const pemp_mpn_weights* w
   }
   return PEMP_OK;
   };
+  // The fused first pass (edge_step_kernel STAGE_FIRST) replaces the embedding launch and pass 0 where pass 0 is a
+  // plain middle pass of the published composed shape: f16x3, attention with the update block pre-applied, no
+  // per-type edge MLP, the caller's composed packs and prebuilt image, steps >= 2 and pass 0 not recorded. Every other
+  // case, a profiler repeat of the passes and PEMP_MPN_TWO_LAUNCH_FIRST keep the two launches -- and so does a forward
+  // the library profiler records (its per-kernel labels stay those of the separate kernels) unless the caller asks for
+  // the fused pass there too (PEMP_MPN_FUSED_FIRST_PROFILED). R0's buffer (ws.EA) is then not touched.
+  const bool fused_first = E > 0 && steps >= 2 && steps - aux - 1 > 0 && !(desc->flags & PEMP_MPN_TWO_LAUNCH_FIRST) &&
+                           desc->precision == PEMP_PREC_F16X3 && desc->aggr == PEMP_AGGR_ATTN && upd_fused && !ept &&
+                           emb_lds && embed_composed(emb_lo, emb_prec, *w) && w->edge_img &&
+                           prof_repeat("edge_step") == 1 &&
+                           (!prof_active() || (desc->flags & PEMP_MPN_FUSED_FIRST_PROFILED));
   auto edge_embed = [&]() -> int {
+  if (fused_first) return PEMP_OK;
   // (the range table is filled behind the edge order on the side stream, edge_prepare)
   if (E > 0 && steps >= 1) {
     // (the label names the fall-backs apart: `wide` reads its weights from global memory, `generic` is the LDS
@@ -4340,6 +4469,14 @@ static int mpn_forward_impl(const pemp_mpn_desc* desc, const pemp_mpn_weights* w
 #ifdef PEMP_STAMPS
       ea.stamps = it == g_diag_stamp_pass ? g_diag_stamps : nullptr;
 #endif
+      if (it == 0 && fused_first) {   // embedding + pass 0 in one launch (the side stream has joined: it reads NT)
+        ea.ea = edge_attr; ea.A = desc->edge_attr_dim;
+        ea.emb_img = w->edge_img + embed_image_offset(*desc, *w);
+        ProfScope prof("edge_first", st);
+        hipLaunchKernelGGL((edge_step_kernel<PEMP_AGGR_ATTN, 0, 2, 1, STAGE_MID | STAGE_FIRST>), dim3(edge_grid),
+                           dim3(64 * EDGE_WAVES), 0, st, ea);
+        PEMP_LAUNCH_CHECK();
+      } else {
       const char* label = !record ? "edge_step" : pub ? "edge_step_head" : "edge_step_head_generic";
       ProfScope prof(label, st);
       // a pass is idempotent (reads r_cur / NT / Q0, rewrites r_next / agg / logits), so the profiler
@@ -4352,6 +4489,7 @@ static int mpn_forward_impl(const pemp_mpn_desc* desc, const pemp_mpn_weights* w
           default: launch_edge_step<PEMP_AGGR_MAX>(ea, record, pub, edge_grid, desc->precision, false, stage, st); break;
         }
         PEMP_LAUNCH_CHECK();
+      }
       }
     }
     // node update + next node table; heads when recorded (the last iteration's heads also fill
@@ -4659,6 +4797,8 @@ extern "C" int pemp_mpn_order_layout(const pemp_mpn_desc* desc, int64_t N, int64
   mpn_carve(nullptr, desc->num_types, N, E, nullptr, offs);
   return PEMP_OK;
 }
+
+extern "C" size_t pemp_mpn_fused_first_lds_bytes(void) { return edge_first_lds_bytes(); }
 
 extern "C" size_t pemp_mpn_edge_image_floats(const pemp_mpn_desc* desc, const pemp_mpn_weights* w) {
   if (!desc || !w || desc->num_types < 1 || desc->num_types > MAXT) return 0;

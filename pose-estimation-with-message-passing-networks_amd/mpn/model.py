@@ -210,6 +210,10 @@ class NodeClassificationMPNSimple(nn.Module):
         self._tensors = None
         self._ws = _lib.Workspace()
         self._desc_key = None
+        # the edge embedding fused into the first edge pass where the library has that form: None (the default) except
+        # in a forward the library profiler records, True there too, False never (two launches, the same bits);
+        # pemp.h PEMP_MPN_TWO_LAUNCH_FIRST / PEMP_MPN_FUSED_FIRST_PROFILED
+        self.fuse_first_pass = None
         self._cap_ok = True   # pemp_step_fully_cap may queue this model's forward (cleared when the library refuses it)
         # one libpemp call addresses r, Q0 and the aggregates with 32-bit byte offsets (pemp_mpn_forward: E, T N
         # < 2^23); larger calls are cut into node blocks no edge crosses (image blocks for construct_graph output)
@@ -244,6 +248,10 @@ class NodeClassificationMPNSimple(nn.Module):
                 self._folded = fold_weights(self, device, self.precision)
             self._folded_key = key
         return self._folded
+
+    def _first_flag(self):
+        f = self.fuse_first_pass
+        return 0 if f is None else _lib.MPN_FUSED_FIRST_PROFILED if f else _lib.MPN_TWO_LAUNCH_FIRST
 
     def _forward_blocks(self, x, edge_attr, edge_index, node_types, kwargs):
         """A call over the library's size limit: the nodes are cut into contiguous blocks that no edge crosses
@@ -308,12 +316,12 @@ class NodeClassificationMPNSimple(nn.Module):
             raise ValueError(f"precision={self.precision!r}: expected one of {sorted(PRECISIONS)}")
         fw = self._weights(dev)                               # may fall back to fp32 (weight range)
         A = edge_attr.shape[1] if edge_attr.dim() == 2 else 1
-        dkey = (A, x.shape[1], self.precision, t_stride)
+        dkey = (A, x.shape[1], self.precision, t_stride, self.fuse_first_pass)
         if self._desc_key != dkey:
             steps, aux = self.edge_steps, self.aux_loss_steps
             self._n_rec = sum(1 for i in range(steps) if i >= steps - aux - 1)
             self._desc = _lib.PempMpnDesc(self.num_types, self.num_joints, steps, aux, self.aggr_code, 64, A,
-                                          x.shape[1], PRECISIONS[self.precision], t_stride, 0)
+                                          x.shape[1], PRECISIONS[self.precision], t_stride, self._first_flag())
             self._desc_ref = ctypes.byref(self._desc)
             self._desc_key = dkey
         desc, n_rec = self._desc_ref, self._n_rec
@@ -393,12 +401,12 @@ class NodeClassificationMPNSimple(nn.Module):
         node_types = joint_det[:, 2]
         fw = self._weights(dev)
         A = edge_attr.shape[1]
-        dkey = (A, x.shape[1], self.precision, 3)
+        dkey = (A, x.shape[1], self.precision, 3, self.fuse_first_pass)
         if self._desc_key != dkey:
             steps, aux = self.edge_steps, self.aux_loss_steps
             self._n_rec = sum(1 for i in range(steps) if i >= steps - aux - 1)
             self._desc = _lib.PempMpnDesc(self.num_types, self.num_joints, steps, aux, self.aggr_code, 64, A,
-                                          x.shape[1], PRECISIONS[self.precision], 3, 0)
+                                          x.shape[1], PRECISIONS[self.precision], 3, self._first_flag())
             self._desc_ref = ctypes.byref(self._desc)
             self._desc_key = dkey
         desc, n_rec = self._desc_ref, self._n_rec
@@ -407,7 +415,7 @@ class NodeClassificationMPNSimple(nn.Module):
                 d = self._desc
                 self._desc_cnt = _lib.PempMpnDesc(d.num_types, d.num_joints, d.steps, d.aux_loss_steps, d.aggr,
                                                   d.hidden, d.edge_attr_dim, d.node_in_dim, d.precision,
-                                                  d.types_stride, _lib.MPN_COUNTS_IN_OFFSETS)
+                                                  d.types_stride, _lib.MPN_COUNTS_IN_OFFSETS | self._first_flag())
                 self._desc_cnt_ref = ctypes.byref(self._desc_cnt)
                 self._desc_cnt_key = dkey
             desc = self._desc_cnt_ref
@@ -439,12 +447,13 @@ class NodeClassificationMPNSimple(nn.Module):
         if e_cap > self._edge_limit or self.num_types * n_cap > self._node_rows_limit:
             return None
         fw = self._weights(dev)
-        dkey = (A, C, self.precision, 3)
+        dkey = (A, C, self.precision, 3, self.fuse_first_pass)
         if getattr(self, "_desc_cnt_key", None) != dkey:
             steps, aux = self.edge_steps, self.aux_loss_steps
             self._n_rec = sum(1 for i in range(steps) if i >= steps - aux - 1)
             self._desc_cnt = _lib.PempMpnDesc(self.num_types, self.num_joints, steps, aux, self.aggr_code, 64, A, C,
-                                              PRECISIONS[self.precision], 3, _lib.MPN_COUNTS_IN_OFFSETS)
+                                              PRECISIONS[self.precision], 3,
+                                              _lib.MPN_COUNTS_IN_OFFSETS | self._first_flag())
             self._desc_cnt_ref = ctypes.byref(self._desc_cnt)
             self._desc_cnt_key = dkey
         L = _lib.lib()
