@@ -40,40 +40,29 @@ constexpr int MAXT = 17;
 constexpr int EDGE_WAVES = 16;   // waves per edge-pass workgroup (one workgroup per CU)
 // edge embedding: EMB_WAVES waves per workgroup, EMB_PER_CU workgroups per CU (each with its own LDS image; the
 // register target follows: EMB_WAVES x EMB_PER_CU / 4 waves per SIMD)
-#ifndef PEMP_EMB_WAVES
-#define PEMP_EMB_WAVES 16
-#endif
-#ifndef PEMP_EMB_PER_CU
-#define PEMP_EMB_PER_CU 1
-#endif
-constexpr int EMB_WAVES = PEMP_EMB_WAVES, EMB_PER_CU = PEMP_EMB_PER_CU;
+// (10 x 2 and 8 x 2 measured against 16 x 1 in round 6, profiles/r06_embed_two_wg.md: not faster)
+constexpr int EMB_WAVES = 16, EMB_PER_CU = 1;
 constexpr int EMB_MIN_WAVES_EU = EMB_WAVES * EMB_PER_CU / 4 > 1 ? EMB_WAVES * EMB_PER_CU / 4 : 1;
-#ifndef PEMP_RESERVE_CUS_DEFAULT
-#define PEMP_RESERVE_CUS_DEFAULT 64
-#endif
-#ifndef PEMP_RESERVE_MIN_EDGES
-#define PEMP_RESERVE_MIN_EDGES 65536
-#endif
 // CUs that the one-workgroup-per-CU launches of a forward over E edges (edge passes, edge embedding, and the prepares'
-// per-workgroup split) spread over. From PEMP_RESERVE_MIN_EDGES edges on, PEMP_RESERVE_CUS of them (rounded down to
+// per-workgroup split) spread over. From RESERVE_MIN_EDGES edges on, PEMP_RESERVE_CUS of them (rounded down to
 // a multiple of 8, so the XCD-aware placement still sees whole XCD rows) are left free: with two batches in flight
 // the other batch's small latency-bound kernels run there instead of waiting for the full-chip launches (c3 +4 %,
 // c3knn10 / c5ms +11 % images/s, one batch at a time -1.5 %). Smaller graphs (batch 1) keep
-// every CU.
-#ifndef PEMP_EMBED_RESERVE
-#define PEMP_EMBED_RESERVE 1   // the edge embedding leaves the reserved CUs free too (0: it spreads over every CU)
-#endif
+// every CU. The edge embedding leaves the reserved CUs free too (spread over every CU: serial steps +1 % / +3.4 %,
+// two batches in flight slower).
+constexpr int RESERVE_CUS_DEFAULT = 64;        // (the PEMP_RESERVE_CUS environment variable overrides it)
+constexpr int64_t RESERVE_MIN_EDGES = 65536;   // (batch 1 stays below it: one batch at a time lost 1.5 % to a reservation)
 // The reservation is capped at a quarter of the device (rounded down to a multiple of 8): 64 of the MI355X's 256
 // CUs, less on a smaller device or a compute partition, where a fixed 64 would take most of the chip.
 static int edge_cus_policy(int cus, int64_t E, int request) {
-  if (E < PEMP_RESERVE_MIN_EDGES || cus <= 8) return cus;
+  if (E < RESERVE_MIN_EDGES || cus <= 8) return cus;
   const int r = std::min(std::max(request, 0), cus / 4) & ~7;
   return cus - r;
 }
 static int edge_cus(int64_t E) {
   static const int request = [] {
     const char* e = getenv("PEMP_RESERVE_CUS");
-    return e ? atoi(e) : PEMP_RESERVE_CUS_DEFAULT;
+    return e ? atoi(e) : RESERVE_CUS_DEFAULT;
   }();
   return edge_cus_policy(num_cus(), E, request);
 }
@@ -87,34 +76,10 @@ __device__ __forceinline__ void st4(float* p, float a, float b, float c, float d
 // (The weight pointers of the GEMM helpers carry no __restrict__: the inliner's noalias scopes would
 // replace the per-variable LDS scopes, and hipcc would then wait for every in-flight LDS-DMA of the edge
 // pass before each weight read.)
-#ifndef PEMP_GEMM_ORDER
-#define PEMP_GEMM_ORDER 0
-#endif
 template <int KB, int OB>
 __device__ __forceinline__ void gemm_frag(const float* W, int ldw, const float (&in)[KB][4],
                                           float (&acc)[OB][4]) {
   const int lane = __lane_id(), i = lane & 15, g = lane >> 4;
-  if (PEMP_GEMM_ORDER == 1) {   // k-outer: OB independent accumulation chains interleaved
-    f32x4 c[OB];
-#pragma unroll
-    for (int ob = 0; ob < OB; ++ob) c[ob] = f32x4{acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]};
-#pragma unroll
-    for (int mb = 0; mb < KB; ++mb) {
-#pragma unroll
-      for (int ob = 0; ob < OB; ++ob) {
-        const float4 w = ld4(W + (16 * ob + i) * ldw + 16 * mb + 4 * g);
-        c[ob] = mfma4(w.x, in[mb][0], c[ob]);
-        c[ob] = mfma4(w.y, in[mb][1], c[ob]);
-        c[ob] = mfma4(w.z, in[mb][2], c[ob]);
-        c[ob] = mfma4(w.w, in[mb][3], c[ob]);
-      }
-    }
-#pragma unroll
-    for (int ob = 0; ob < OB; ++ob) {
-      acc[ob][0] = c[ob][0]; acc[ob][1] = c[ob][1]; acc[ob][2] = c[ob][2]; acc[ob][3] = c[ob][3];
-    }
-    return;
-  }
 #pragma unroll
   for (int ob = 0; ob < OB; ++ob) {
     f32x4 c = {acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]};
@@ -1211,11 +1176,8 @@ static bool embed_fixed_shape(const EmbedLayout& L) {
   return true;
 }
 // the composed form of the fixed f16x3 embedding (embed_tile_fixed COMP) runs when the caller supplied its packs
-#ifndef PEMP_EMBED_COMPOSE
-#define PEMP_EMBED_COMPOSE 1
-#endif
 static bool embed_composed(const EmbedLayout& L, int prec, const pemp_mpn_weights& w) {
-  return PEMP_EMBED_COMPOSE && prec == PEMP_PREC_F16X3 && embed_fixed_shape(L) && w.emb_comp_bf && w.emb_comp_b;
+  return prec == PEMP_PREC_F16X3 && embed_fixed_shape(L) && w.emb_comp_bf && w.emb_comp_b;
 }
 
 // Stage one 64x64 edge-pass matrix into LDS (PREC 0: fp32 rows of LDW; PREC 1: interleaved bf16)
@@ -1836,31 +1798,11 @@ __device__ __forceinline__ void dma_wait() {
 #endif
 }
 
-#ifndef PEMP_FAST_EXP
-#define PEMP_FAST_EXP 1
-#endif
-#ifndef PEMP_GATHER_FIRST
-#define PEMP_GATHER_FIRST 0
-#endif
-#ifndef PEMP_PRIO
-#define PEMP_PRIO 1
-#endif
-// softmax exponent: expf (correctly rounded to ~1 ulp) or the bare v_exp_f32 path (__expf, the default: the
-// exponent is <= 0 and its relative error |x| 2^-24 ln 2 stays far below the 1e-4 logit bar)
-__device__ __forceinline__ float pemp_exp(float x) { return PEMP_FAST_EXP ? __expf(x) : expf(x); }
-#ifndef PEMP_FAST_RCP
-#define PEMP_FAST_RCP 1
-#endif
-// segment normaliser: IEEE division or v_rcp_f32 (1 ulp)
-__device__ __forceinline__ float pemp_rcp(float x) { return PEMP_FAST_RCP ? __builtin_amdgcn_rcpf(x) : 1.0f / x; }
-// the fused first pass (STAGE_FIRST): Q0 kept in registers from the embedding to the r_next GEMM (0) or read back by
-// the wave that stored it (1, the default: DESIGN §4)
-#ifndef PEMP_FIRST_Q0_RELOAD
-#define PEMP_FIRST_Q0_RELOAD 1
-#endif
-#ifndef PEMP_XCD_MAP
-#define PEMP_XCD_MAP 1
-#endif
+// softmax exponent: the bare v_exp_f32 path (__expf) instead of expf (correctly rounded to ~1 ulp): the exponent is
+// <= 0 and its relative error |x| 2^-24 ln 2 stays far below the 1e-4 logit bar
+__device__ __forceinline__ float pemp_exp(float x) { return __expf(x); }
+// segment normaliser: v_rcp_f32 (1 ulp) instead of the IEEE division
+__device__ __forceinline__ float pemp_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 template <int AGG, int HEAD, int PREC, int UPD, int STAGE>
 __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_kernel(EdgeStepArgs a) {
   constexpr int NW = edge_waves_s<HEAD, STAGE>();
@@ -1901,7 +1843,7 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
   int lb = blockIdx.x;
   // (round 6: placing each XCD's workgroups on an eighth of the targets for every type instead -- one image's node-table
   // rows per XCD -- fetched 113.5 vs 107.8 MB per c3 pass and was no faster; profiles/r06_build_counts_xcd.md)
-  if (PEMP_XCD_MAP && (gridDim.x & 7) == 0) lb = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  if ((gridDim.x & 7) == 0) lb = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
   const int4 rg = a.ranges[lb * NW + wave];
   // wave-uniform by construction; readfirstlane tells hipcc (else the tile loop and every buffer access
   // downstream are compiled as divergent)
@@ -2014,14 +1956,12 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
   int tile_no = 0;
   for (int base = first; base < end; base += 16, ++tile_no) {
     if (tile_no < 4) EDGE_STAMP(3 + 3 * tile_no);
-#if PEMP_PRIO
     // progress-ordered issue priority: a wave that has finished fewer tiles than its SIMD partners goes first
     // (the hardware otherwise favours the oldest wave, which then finishes long before the youngest)
     if (tile_no == 0) __builtin_amdgcn_s_setprio(3);
     else if (tile_no == 1) __builtin_amdgcn_s_setprio(2);
     else if (tile_no == 2) __builtin_amdgcn_s_setprio(1);
     else if (tile_no == 3) __builtin_amdgcn_s_setprio(0);
-#endif
     // opaque zero: keeps the compiler from hoisting the LDS weight fragments out of the loop
     // (192+ VGPRs of loop-invariant loads would spill)
     int z = 0;
@@ -2104,18 +2044,17 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
       }
     }
     if constexpr (FIRST) {
-      // the P_t rows (read at the message GEMM) and, with PEMP_FIRST_Q0_RELOAD, this wave's own Q0 rows back through
-      // the descriptor they were stored with (read at the r_next GEMM): issued once the A / B rows are consumed
+      // the P_t rows (read at the message GEMM) and this wave's own Q0 rows back through the descriptor they were
+      // stored with (read at the r_next GEMM; kept in 16 registers from the embedding instead they cost more,
+      // DESIGN §4): issued once the A / B rows are consumed
 #pragma unroll
       for (int ob = 0; ob < 4; ++ob) asm volatile("" ::"v"(h[ob][0]), "v"(h[ob][1]), "v"(h[ob][2]), "v"(h[ob][3]));
       gather_p(dst);
-#if PEMP_FIRST_Q0_RELOAD
 #pragma unroll
       for (int ob = 0; ob < 4; ++ob) {
         const float4 q = bld4(rs_q0, min(p, end - 1) * 256 + 16 * g + 64 * ob);
         q0r[ob][0] = q.x; q0r[ob][1] = q.y; q0r[ob][2] = q.z; q0r[ob][3] = q.w;
       }
-#endif
     }
     // other passes: the r rows of tile k+1 into the buffer this tile's rows were read from, once every
     // gather of this tile has returned (the compiler's waits on those would otherwise also wait on the DMA)
@@ -2304,12 +2243,6 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
         for (int r = 0; r < 4; ++r) cacc[ob][r] = dppf<DPP_SHL15>(v[ob][r], 0.0f);   // lane 15 -> lane 0
     }
     have_carry = carry_out;
-#if PEMP_GATHER_FIRST
-    // the next tile's gathers ahead of this tile's aggregate stores: waiting for them at the next tile then does
-    // not wait for those stores too (vmcnt retires in issue order)
-    if (!FIRST) gather_nt(dst_n, src_n, more);
-    if (HEAD == 1) orig_t = bld1(rs_orig, 4 * min(p + 16, end - 1));
-#endif
     {
       // the aggregate leaves the f16x3 domain here (dom_inv)
       const float inv = ((AGG == PEMP_AGGR_ATTN) ? pemp_rcp(l + 1e-12f) : (AGG == PEMP_AGGR_MEAN) ? pemp_rcp(l) : 1.0f) *
@@ -2331,12 +2264,11 @@ __global__ __launch_bounds__((64 * edge_waves_s<HEAD, STAGE>())) void edge_step_
         if (g == 0) { rec[64] = M; rec[65] = l; }
       }
     }
-#if !PEMP_GATHER_FIRST
-    {   // the next tile's gathers, unconditional (past the range: OOB offsets, no traffic)
+    {   // the next tile's gathers, unconditional (past the range: OOB offsets, no traffic). (Issued ahead of this
+      // tile's aggregate stores instead, so that the next tile's wait skips those stores: no gain)
       if (!FIRST) gather_nt(dst_n, src_n, more);
       if (HEAD == 1) orig_t = bld1(rs_orig, 4 * min(p + 16, end - 1));
     }
-#endif
 #ifdef PEMP_STAMPS
     asm volatile("" ::"v"(v[0][0]), "v"(v[3][3]));
     if (tile_no < 4) EDGE_STAMP(5 + 3 * tile_no);
@@ -2968,28 +2900,16 @@ struct NodeTableArgs {
   const float* upd_b;
 };
 
-#ifndef PEMP_NODE_ON_SIDE
-#define PEMP_NODE_ON_SIDE 1   // the first node step on the prelude side stream, the edge prelude on the launch stream
-#endif
-#ifndef PEMP_SIDE_MIN_E
-#define PEMP_SIDE_MIN_E 65536   // below this many edges (capacity) the prelude stays on the launch stream: at c2 (one
-                                // image, ~22k edges) the fork and join waits (7 + 11 us) cost more than the overlap
-                                // buys: step span 141 vs 165 us, images/s +18 % (profiles/r06_c2_serial_prelude.md)
-#endif
-#ifndef EMBED_ON_SIDE
-#define EMBED_ON_SIDE 1   // capacity mode: the edge embedding on the prelude side stream (see mpn_forward_impl)
-#endif
-#ifndef NODE_SUM_TABLE
-#define NODE_SUM_TABLE 1   // the middle steps' node update fused into the node-table launch
-#endif
-#ifndef NODE_SUM_TABLE_MAX_MB
-#define NODE_SUM_TABLE_MAX_MB 16   // ... while its aggregate re-reads (N T 256 B x column groups) stay below this
-#endif
-#ifndef PEMP_TBL_TILES
-#define PEMP_TBL_TILES 2   // (1 / 2 / 4 / 8 measured: 2 gives the shortest isolated MPN, c3knn10 0.423-0.426 vs 0.435 ms
-                           // with 4, c3 0.235 vs 0.239 ms; tools/experiments/round5/nn.sh)
-#endif
-constexpr int TBL_TILES = PEMP_TBL_TILES;   // 16-node tiles per workgroup
+// below this many edges (capacity) the prelude stays on the launch stream: at c2 (one image, ~22k edges) the fork
+// and join waits (7 + 11 us) cost more than the overlap buys: step span 141 vs 165 us, images/s +18 %
+// (profiles/r06_c2_serial_prelude.md)
+constexpr int64_t SIDE_MIN_E = 65536;
+// the middle steps' node update runs inside the node-table launch while its aggregate re-reads (N T 256 B x column
+// groups) stay below this many MB
+constexpr int64_t NODE_SUM_TABLE_MAX_MB = 16;
+// (1 / 2 / 4 / 8 measured: 2 gives the shortest isolated MPN, c3knn10 0.423-0.426 vs 0.435 ms with 4, c3 0.235 vs
+// 0.239 ms; tools/experiments/round5/nn.sh)
+constexpr int TBL_TILES = 2;           // 16-node tiles per workgroup
 
 // SUM: the node update x = ReLU(b + sum_t agg[n, t]) (node_rows_kernel ROWS_SUM, same operations and order) is
 // computed here for the tile's 16 rows, by every column group of the tile (the aggregates are re-read from L2 by
@@ -3170,7 +3090,7 @@ static void launch_edge_step_p(const EdgeStepArgs& a, bool head, bool pub, int g
 
 static bool edge_upd_fused(const pemp_mpn_desc& d, const pemp_mpn_weights& w);
 static bool edge_pub_head(const pemp_mpn_desc& d, const pemp_mpn_weights& w);
-// the edge embedding's arithmetic (mpn_forward_impl's emb_prec) and where its LDS image follows the passes' image
+// the edge embedding's arithmetic (ForwardPlan::emb_prec) and where its LDS image follows the passes' image
 static int embed_prec(const pemp_mpn_desc& d, const pemp_mpn_weights& w) {
   return d.precision != PEMP_PREC_FP32 && w.emb_bf ? d.precision : PEMP_PREC_FP32;
 }
@@ -3194,13 +3114,18 @@ static EdgeImgArgs edge_image_args(const pemp_mpn_desc& d, const pemp_mpn_weight
 
 // whether the edge passes pre-apply the update block (UPD) and carry the published head (HEAD 1)
 static bool edge_upd_fused(const pemp_mpn_desc& d, const pemp_mpn_weights& w) {
-#ifdef PEMP_NO_UPD_FUSE   // (experiment builds only, DESIGN §4: the update MLP on the nodes)
-  return false;
-#endif
   return (d.aggr == PEMP_AGGR_ATTN || d.aggr == PEMP_AGGR_MEAN) && w.upd_w && (d.precision == PEMP_PREC_FP32 || w.upd_bf);
 }
 static bool edge_pub_head(const pemp_mpn_desc& d, const pemp_mpn_weights& w) {
   return published_head(w.edge_head) && (d.precision == PEMP_PREC_FP32 || w.head_bf);
+}
+
+// The one dispatch from a run-time PEMP_PREC_* to a template argument: f(std::integral_constant<int, PREC>{}).
+template <class F>
+static void with_prec(int prec, F&& f) {
+  if (prec == PEMP_PREC_F16X3) f(std::integral_constant<int, PEMP_PREC_F16X3>{});
+  else if (prec == PEMP_PREC_BF16X3) f(std::integral_constant<int, PEMP_PREC_BF16X3>{});
+  else f(std::integral_constant<int, PEMP_PREC_FP32>{});
 }
 
 // UPD is instantiated for the linear aggregations only (U · max(m) != max(U · m))
@@ -3208,16 +3133,10 @@ template <int AGG>
 static void launch_edge_step(const EdgeStepArgs& a, bool head, bool pub, int grid, int prec, bool upd, int stage,
                              hipStream_t st) {
   constexpr int U = AGG == PEMP_AGGR_ATTN || AGG == PEMP_AGGR_MEAN ? 1 : 0;
-  if (prec == PEMP_PREC_F16X3) {
-    if (U && upd) launch_edge_step_p<AGG, 2, U>(a, head, pub, grid, stage, st);
-    else launch_edge_step_p<AGG, 2, 0>(a, head, pub, grid, stage, st);
-  } else if (prec == PEMP_PREC_BF16X3) {
-    if (U && upd) launch_edge_step_p<AGG, 1, U>(a, head, pub, grid, stage, st);
-    else launch_edge_step_p<AGG, 1, 0>(a, head, pub, grid, stage, st);
-  } else {
-    if (U && upd) launch_edge_step_p<AGG, 0, U>(a, head, pub, grid, stage, st);
-    else launch_edge_step_p<AGG, 0, 0>(a, head, pub, grid, stage, st);
-  }
+  with_prec(prec, [&](auto P) {
+    if (U && upd) launch_edge_step_p<AGG, decltype(P)::value, U>(a, head, pub, grid, stage, st);
+    else launch_edge_step_p<AGG, decltype(P)::value, 0>(a, head, pub, grid, stage, st);
+  });
 }
 
 static int rows_mlp(const char* label, const pemp_mlp& m, const float* in, int64_t ld_in, int64_t M, float* out,
@@ -3267,10 +3186,7 @@ static StagePlan node_image_plan(const pemp_mpn_weights& w) {
 // with E_t = sum_b n_{b,t} (n_b - 1). Identical arrays to launch_prepare's (tested bit for bit).
 constexpr int FULLY_MAXB = 64;      // images per batch
 constexpr int FULLY_MAXN = 2048;    // nodes per image (LDS lists)
-#ifndef PEMP_FULLY_PARTS
-#define PEMP_FULLY_PARTS 4
-#endif
-constexpr int FULLY_PARTS = PEMP_FULLY_PARTS;   // threads per (type, target) segment in fully_prepare_kernel
+constexpr int FULLY_PARTS = 4;   // threads per (type, target) segment in fully_prepare_kernel
 // Capacity mode (pemp_mpn_forward_fully_cap): the batch's N = sum n_b and E = sum n_b (n_b - 1) from the detection
 // counts on the device, before the host has them. ne = (N, E, overflow); a batch past any capacity (an image over
 // the detection capacity, N > n_cap or E > e_cap: the capacity graph build wrote nothing) gets (0, 0, 1), and every
@@ -3988,8 +3904,6 @@ extern "C" size_t pemp_mpn_workspace_size(const pemp_mpn_desc* desc, int64_t N, 
 // isolated forward 0.252 vs 0.242 ms, re-captured whenever N / E or the allocator's buffers change). The
 // capacity-mode forward, whose arguments repeat from step to step, is replayed from a graph:
 // pemp_mpn_forward_fully_cap.)
-// fully_node_off != NULL: edge_index is the fully graph of the batch with these per-image node
-// offsets (device, [fully_B + 1]) -> the closed-form prepare (fully_prepare_kernel)
 #ifdef PEMP_STAMPS
 // diagnostic builds: the edge pass `g_diag_stamp_pass` of every forward records per-wave phase stamps
 static unsigned long long* g_diag_stamps = nullptr;
@@ -4001,7 +3915,7 @@ extern "C" int pemp_diag_stamps(void* buf, int pass) {
 }
 #endif
 
-// ---- side stream of a launch stream (the concurrent edge prelude of mpn_forward_impl) ----------------
+// ---- side stream of a launch stream (the concurrent prelude of a forward, Forward::prelude) ----------------
 struct SideStream {
   hipStream_t s = nullptr;
   hipEvent_t fork = nullptr, join = nullptr;
@@ -4014,9 +3928,6 @@ static bool serial_prelude() {
 }
 
 // one per (device, launch stream), created on first use and kept; nullptr if HIP refuses (serial then)
-#ifndef PEMP_SIDE_PRIO
-#define PEMP_SIDE_PRIO 0
-#endif
 static SideStream* side_stream_for(hipStream_t st) {
   static std::mutex mu;
   static std::map<std::pair<int, hipStream_t>, SideStream*> table;
@@ -4032,11 +3943,9 @@ static SideStream* side_stream_for(hipStream_t st) {
   if (it != table.end()) return it->second;
   if (dev != cur && hipSetDevice(dev) != hipSuccess) return nullptr;
   SideStream* ss = new SideStream();
-  int prio_lo = 0, prio_hi = 0;   // PEMP_SIDE_PRIO: the edge prelude's stream at the device's highest priority
-  if (!PEMP_SIDE_PRIO || hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_hi = 0;
-  const bool ok = (PEMP_SIDE_PRIO && prio_hi != 0
-                       ? hipStreamCreateWithPriority(&ss->s, hipStreamNonBlocking, prio_hi)
-                       : hipStreamCreateWithFlags(&ss->s, hipStreamNonBlocking)) == hipSuccess &&
+  // (default priority: at the device's highest the stream gained nothing at c3 / c5 and lost 12 % at c3knn10,
+  // DESIGN.md section 4)
+  const bool ok = hipStreamCreateWithFlags(&ss->s, hipStreamNonBlocking) == hipSuccess &&
                   hipEventCreateWithFlags(&ss->fork, hipEventDisableTiming) == hipSuccess &&
                   hipEventCreateWithFlags(&ss->join, hipEventDisableTiming) == hipSuccess;
   if (dev != cur) (void)hipSetDevice(cur);
@@ -4048,14 +3957,46 @@ static SideStream* side_stream_for(hipStream_t st) {
   return ss;
 }
 
-static int mpn_forward_impl(const pemp_mpn_desc* desc, const pemp_mpn_weights* w, const float* x,
-                            const float* edge_attr, const int64_t* edge_index, const int64_t* node_types,
-                            int64_t N, int64_t E, float* edge_logits, float* node_logits, float* class_logits,
-                            void* workspace, size_t workspace_bytes, void* stream, const int64_t* fully_node_off,
-                            int fully_B, int fully_nmax, bool sym = false, const int32_t* cap_ndet = nullptr,
-                            int cap_det = 0, const KnnPrepArgs* knn = nullptr, const int64_t* cap_ne = nullptr) {
+// ---- the inference forward: what a call is given (ForwardCall), its argument checks, everything derived from it
+// on the host (ForwardPlan), and the launches (Forward) ------------------------------------------------------------
+// where the type-major edge order of a forward comes from
+struct EdgeOrder {
+  enum Kind { SORT, FULLY, SYM, KNN } kind = SORT;   // SORT: the sorting prepare on edge_index (launch_prepare)
+  // FULLY: edge_index is the fully graph of the batch with these per-image node offsets (device, [B + 1]) -> the
+  // closed-form prepare (fully_prepare_kernel); nmax bounds the nodes of one image
+  const int64_t* node_off = nullptr;
+  int B = 0, nmax = 0;
+  const KnnPrepArgs* knn = nullptr;   // KNN: the graph build's row lists (knn_prepare_kernel)
+};
+
+// capacity mode (pemp_mpn_forward_fully_cap): N and E are capacities; the device-side counts come first -- from the
+// capacity graph build (ne: PEMP_MPN_COUNTS_IN_OFFSETS) or from a launch of their own
+struct CapMode {
+  const int32_t* n_det = nullptr;   // detections per image (device); NULL: an exact forward
+  int det_cap = 0;
+  const int64_t* ne = nullptr;
+};
+
+struct ForwardCall {
+  const pemp_mpn_desc* desc;
+  const pemp_mpn_weights* w;
+  const float *x, *edge_attr;
+  const int64_t *edge_index, *node_types;
+  int64_t N, E;
+  float *edge_logits, *node_logits, *class_logits;   // bases of the three logit arrays
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+  EdgeOrder order;
+  CapMode cap;
+};
+
+static int check_forward_args(const ForwardCall& c) {
+  const pemp_mpn_desc* desc = c.desc;
+  const pemp_mpn_weights* w = c.w;
   PEMP_CHECK_ARG(desc && w, "pemp_mpn_forward: null desc/weights");
   const int T = desc->num_types, J = desc->num_joints;
+  const int64_t N = c.N, E = c.E;
   PEMP_CHECK_ARG(desc->hidden == 64, "pemp_mpn_forward: hidden width must be 64 (got %d)", desc->hidden);
   PEMP_CHECK_ARG(T >= 1 && T <= MAXT, "pemp_mpn_forward: num_types must be in [1, %d]", MAXT);
   // (the edge passes address r, Q0 and the aggregates with 32-bit byte offsets: E, T N < 2^23; the sorted target
@@ -4106,408 +4047,444 @@ static int mpn_forward_impl(const pemp_mpn_desc* desc, const pemp_mpn_weights* w
   PEMP_CHECK_ARG(desc->precision == PEMP_PREC_FP32 ||
                      (w->e1_bf && w->e2_bf && w->msg_bf && w->pre_bf && (w->emb_bf || !mlp_ok(w->edge_emb, 64, 64))),
                  "pemp_mpn_forward: split precisions need the e1_bf / e2_bf / msg_bf / pre_bf / emb_bf weight packs");
-  PEMP_CHECK_ARG(N == 0 || (x && node_logits && class_logits && node_types), "pemp_mpn_forward: null node tensors");
-  PEMP_CHECK_ARG(E == 0 || (edge_attr && (edge_index || fully_node_off) && edge_logits), "pemp_mpn_forward: null edge tensors");
+  PEMP_CHECK_ARG(N == 0 || (c.x && c.node_logits && c.class_logits && c.node_types),
+                 "pemp_mpn_forward: null node tensors");
+  PEMP_CHECK_ARG(E == 0 || (c.edge_attr && (c.edge_index || c.order.kind == EdgeOrder::FULLY) && c.edge_logits),
+                 "pemp_mpn_forward: null edge tensors");
   size_t need = 0;
   mpn_carve(nullptr, T, N, E, &need);
-  if (workspace_bytes < need) {
-    set_error("pemp_mpn_forward: workspace %zu < %zu bytes", workspace_bytes, need);
+  if (c.workspace_bytes < need) {
+    set_error("pemp_mpn_forward: workspace %zu < %zu bytes", c.workspace_bytes, need);
     return PEMP_ERR_WORKSPACE;
   }
-  if (N == 0) return PEMP_OK;
-  PEMP_CHECK_ARG(!(E > 0 && N == 0), "pemp_mpn_forward: edges without nodes");
-  const MpnWs ws = mpn_carve(workspace, T, N, E, nullptr);
-  const hipStream_t st = as_stream(stream);
-  const int64_t tstride = desc->types_stride > 0 ? desc->types_stride : 1;   // node_types may be a strided view
-  // capacity mode (pemp_mpn_forward_fully_cap): N and E are capacities; the device-side counts come first -- from
-  // the capacity graph build (cap_ne: PEMP_MPN_COUNTS_IN_OFFSETS) or from a launch of their own
-  const int64_t* const ne = cap_ne ? cap_ne : cap_ndet ? reinterpret_cast<int64_t*>(ws.err + 8) : nullptr;
-  if (cap_ndet && !cap_ne) {
-    hipLaunchKernelGGL(cap_counts_kernel, dim3(1), dim3(256), 0, st, cap_ndet, fully_B, cap_det, N, E,
-                       reinterpret_cast<int64_t*>(ws.err + 8));
-    PEMP_LAUNCH_CHECK();
-  }
-  const int64_t K = (int64_t)T * N;
+  return PEMP_OK;
+}
 
-  const bool fused_heads_ = node_heads_fused(*w);
-  const bool fused_embed_ = node_embed_fused(*w);
-  // LDS image of the node-side MLPs: the caller's (pemp_mpn_node_image) or built here
-  const float* node_img = w->node_img;
-  if (!node_img && (fused_heads_ || fused_embed_)) {
-    const StagePlan plan = node_image_plan(*w);
-    hipLaunchKernelGGL(stage_image_kernel, dim3((unsigned)std::min(64, (plan.total + 255) / 256)), dim3(256), 0, st, plan,
-                       ws.img);
-    PEMP_LAUNCH_CHECK();
-    node_img = ws.img;
-  }
+// how the node update of an iteration runs (node_step's mode: a ROWS_* mode of node_rows_kernel, or the update MLP
+// in a launch of its own ahead of it)
+constexpr int NODE_UPDATE_MLP = -1;
 
-  // ---- edge embedding: its own launch writes Q0 and R0 = Q0 + W1_e_cur · e_init (edge_embed_kernel;
-  // the published shape takes the straight-line edge_embed_kernel<PREC, true>) ----
-  int rc = 0;
-  const int steps = desc->steps, aux = desc->aux_loss_steps;
+// Everything a forward derives from its call on the host, each value once. Nothing here launches.
+struct ForwardPlan {
+  int T, J, steps, aux;
+  int64_t tstride;        // node_types may be a strided view
+  bool upd_fused;         // U_t pre-applied in the edge pass: the node update is a sum (edge_upd_fused)
+  bool pub_head;          // the published head's weights ride in the passes' LDS image
+  bool ept;               // EDGE_MLP per_type
+  // the edge embedding: in LDS (else the `wide` kernel, weights from global memory), its arithmetic and LDS layout,
+  // and which form of the LDS kernel runs (`generic`: the runtime-shaped form for a shape off the fixed layout -- no
+  // precision has a straight-line kernel for it)
+  bool emb_lds, emb_generic, comp, fixed;
+  int emb_prec;
+  EmbedLayout emb_lo;
+  bool fused_heads, fused_embed;   // the node / class heads and the node embedding inside node_rows_kernel
+  int edge_grid;                   // workgroups of the edge passes (and of the prepares' per-workgroup split)
+  int NO, table_prec, table_groups;
+  unsigned node_grid, table_grid, table_grid1;
+  int node_mode;
+  bool sum_in_table;    // middle steps: the node update inside the node-table launch (node_step)
+  bool fused_first;
+  bool side;            // the first node step on the side stream (Forward::prelude)
+};
+
+static ForwardPlan plan_forward(const ForwardCall& c) {
+  const pemp_mpn_desc& d = *c.desc;
+  const pemp_mpn_weights& w = *c.w;
+  const int64_t N = c.N, E = c.E;
+  ForwardPlan p{};
+  p.T = d.num_types; p.J = d.num_joints; p.steps = d.steps; p.aux = d.aux_loss_steps;
+  p.tstride = d.types_stride > 0 ? d.types_stride : 1;
   // U_t pre-applied in the edge pass (linear aggregations with an update MLP): the node update is a sum
   // (ATTN / MEAN only: for the unnormalised SUM the reordered fp32 rounding of sum_e U m_e vs
   // U sum_e m_e grows with the in-degree past the logit tolerance)
-  const bool upd_fused = edge_upd_fused(*desc, *w);
-  const bool emb_lds = mlp_ok(w->edge_emb, 64, 64);
-  const int emb_prec = desc->precision != PEMP_PREC_FP32 && w->emb_bf ? desc->precision : PEMP_PREC_FP32;
-  const EmbedLayout emb_lo = embed_layout(w->edge_emb, emb_prec);
-  const bool ept = w->ept_l1_w != nullptr;
-  const int edge_grid = std::max(edge_cus(E), T);   // >= wg_start[T] (see mpn_scan_kernel)
-  const bool pub_head = edge_pub_head(*desc, *w);
-  // the edge-pass weight image: the caller's (pemp_mpn_edge_image, built once per weight set) or built here
-  const float* eimg = w->edge_img;
-  if (!eimg && E > 0 && steps >= 1) {
-    EdgeImgArgs ia = edge_image_args(*desc, *w, upd_fused, pub_head, ws.eimg);
-    hipLaunchKernelGGL(edge_image_kernel, dim3(16, (unsigned)T), dim3(256), 0, st, ia);
-    PEMP_LAUNCH_CHECK();
-    eimg = ws.eimg;
-  }
-  hipStream_t pst = st;                           // stream of the edge prelude (a side stream, below)
-  // the edge prelude in two parts: the edge order (prepare), then the range table + edge embedding
-  auto edge_prepare = [&]() -> int {
-  if (!(desc->flags & PEMP_MPN_PREPARED)) {
-    if (fully_node_off && N > 0) {
-      FullyPrepArgs fa{fully_node_off, fully_B, node_types, tstride, N, T, std::max(edge_cus(E), T),
-                       ws.seg, ws.wg_start, ws.s_src, ws.s_dst, ws.s_orig, ws.err, ne};
-      // FULLY_PARTS threads per (type, target) segment (a per-edge mapping with binary searches measured 41 us
-      // vs 15 us at C3)
-      const unsigned gx =
-          (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)T * fully_nmax * FULLY_PARTS + 511) / 512));
-      ProfScope prof("mpn_prepare_fully", pst);
-      hipLaunchKernelGGL(fully_prepare_kernel, dim3(gx, (unsigned)fully_B), dim3(256), 0, pst, fa);
-      PEMP_LAUNCH_CHECK();
-    } else if (knn && N > 0) {
-      KnnPrepArgs ka = *knn;
-      ka.types = node_types;
-      ka.ts = tstride;
-      ka.N = N;
-      ka.E = E;
-      ka.T = T;
-      ka.G = std::max(edge_cus(E), T);
-      ka.seg = ws.seg;
-      ka.wg_start = ws.wg_start;
-      ka.s_src = ws.s_src;
-      ka.s_dst = ws.s_dst;
-      ka.s_orig = ws.s_orig;
-      ka.err = ws.err;
-      ProfScope prof("mpn_prepare_knn", pst);
-      hipLaunchKernelGGL(knn_prepare_kernel, dim3((unsigned)T, (unsigned)((N + KP_CH - 1) / KP_CH)), dim3(1024), 0, pst,
-                         ka);
-      PEMP_LAUNCH_CHECK();
-    } else if (sym && N > 0) {
-      const int rc0 = launch_prepare_sym(desc, edge_index, node_types, N, E, ws, pst);
-      if (rc0) return rc0;
-    } else {
-      const int rc0 = launch_prepare(desc, edge_index, node_types, N, E, ws, pst);
-      if (rc0) return rc0;
-    }
-  }
-  // the passes' per-wave range table (static across iterations), right behind the order on the prelude stream:
-  // its chains of dependent small loads stay off the edge embedding's workgroups
-  if (E > 0 && steps >= 1) {
-    // (behind the range table's blocks: the per-edge segment positions, one edge per thread)
-    const int rg_blocks = std::min(64, (edge_grid * (EDGE_WAVES + 12) + 255) / 256);
-    const int pos_blocks = (int)std::min<int64_t>(1024, (E + 255) / 256);
-    hipLaunchKernelGGL(edge_ranges_kernel, dim3((unsigned)(rg_blocks + pos_blocks)), dim3(256), 0, pst, ws.seg,
-                       ws.wg_start, ws.s_dst, T, N, edge_grid, ws.ranges, ne, rg_blocks);
-    PEMP_LAUNCH_CHECK();
-  }
-  return PEMP_OK;
-  };
+  p.upd_fused = edge_upd_fused(d, w);
+  p.pub_head = edge_pub_head(d, w);
+  p.ept = w.ept_l1_w != nullptr;
+  p.emb_lds = mlp_ok(w.edge_emb, 64, 64);
+  p.emb_prec = embed_prec(d, w);
+  p.emb_lo = embed_layout(w.edge_emb, p.emb_prec);
+  p.emb_generic = p.emb_lds && !embed_fixed_shape(p.emb_prec == PEMP_PREC_FP32
+                                                      ? embed_layout(w.edge_emb, PEMP_PREC_F16X3)
+                                                      : p.emb_lo);
+  p.fixed = embed_fixed_shape(p.emb_lo);
+  p.comp = embed_composed(p.emb_lo, p.emb_prec, w);
+  p.fused_heads = node_heads_fused(w);
+  p.fused_embed = node_embed_fused(w);   // (embedding widths > 128 would not fit the node step's LDS rows)
+  p.edge_grid = std::max(edge_cus(E), p.T);   // >= wg_start[T] (see mpn_scan_kernel)
+  p.NO = 128 + 64 * p.T;
+  p.table_prec = d.precision != PEMP_PREC_FP32 && w.pre_bf ? d.precision : PEMP_PREC_FP32;
+  p.table_groups = (p.NO / 16 + 3) / 4;
+  p.node_grid = (unsigned)((N + 15) / 16);
+  p.table_grid = (unsigned)(((N + 16 * TBL_TILES - 1) / (16 * TBL_TILES)) * p.table_groups);
+  p.table_grid1 = (unsigned)(((N + 15) / 16) * p.table_groups);
+  p.node_mode = p.upd_fused ? ROWS_SUM : (w.upd_w || w.upd_mlp.n_layers > 0) ? NODE_UPDATE_MLP : ROWS_COPY;
+  // (every column group re-reads the tile's aggregates: worth it while those re-reads stay small -- C2 -- not at
+  // C3, where they are ~100 MB per call and the fused launch only ties the two it replaces. Round 6: a wide form,
+  // 16 waves = 256 columns per workgroup so a tile's aggregates are summed 5 instead of 19 times, took 24 us per
+  // call against 8 + 10 us for the two launches at c3 / c3knn10 (profiles/r06_node_sum_wide.md); not kept.)
+  p.sum_in_table = !p.ept && N * p.T * 256 * (int64_t)p.table_groups <= NODE_SUM_TABLE_MAX_MB << 20;
   // The fused first pass (edge_step_kernel STAGE_FIRST) replaces the embedding launch and pass 0 where pass 0 is a
   // plain middle pass of the published composed shape: f16x3, attention with the update block pre-applied, no
   // per-type edge MLP, the caller's composed packs and prebuilt image, steps >= 2 and pass 0 not recorded. Every other
   // case, a profiler repeat of the passes and PEMP_MPN_TWO_LAUNCH_FIRST keep the two launches -- and so does a forward
   // the library profiler records (its per-kernel labels stay those of the separate kernels) unless the caller asks for
   // the fused pass there too (PEMP_MPN_FUSED_FIRST_PROFILED). R0's buffer (ws.EA) is then not touched.
-  const bool fused_first = E > 0 && steps >= 2 && steps - aux - 1 > 0 && !(desc->flags & PEMP_MPN_TWO_LAUNCH_FIRST) &&
-                           desc->precision == PEMP_PREC_F16X3 && desc->aggr == PEMP_AGGR_ATTN && upd_fused && !ept &&
-                           emb_lds && embed_composed(emb_lo, emb_prec, *w) && w->edge_img &&
-                           prof_repeat("edge_step") == 1 &&
-                           (!prof_active() || (desc->flags & PEMP_MPN_FUSED_FIRST_PROFILED));
-  auto edge_embed = [&]() -> int {
-  if (fused_first) return PEMP_OK;
-  // (the range table is filled behind the edge order on the side stream, edge_prepare)
-  if (E > 0 && steps >= 1) {
-    // (the label names the fall-backs apart: `wide` reads its weights from global memory, `generic` is the LDS
-    // kernel's runtime-shaped form for a shape off the fixed layout -- no precision has a straight-line kernel for it)
-    const bool emb_generic = emb_lds && !embed_fixed_shape(emb_prec == PEMP_PREC_FP32
-                                                               ? embed_layout(w->edge_emb, PEMP_PREC_F16X3)
-                                                               : emb_lo);
-    ProfScope prof(!emb_lds ? "edge_embed_wide" : emb_generic ? "edge_embed_generic" : "edge_embed", pst);
-    if (emb_lds) {
-      const int grid = (int)std::min<int64_t>((int64_t)(PEMP_EMBED_RESERVE ? edge_cus(E) : num_cus()) * EMB_PER_CU,
+  p.fused_first = E > 0 && p.steps >= 2 && p.steps - p.aux - 1 > 0 && !(d.flags & PEMP_MPN_TWO_LAUNCH_FIRST) &&
+                  d.precision == PEMP_PREC_F16X3 && d.aggr == PEMP_AGGR_ATTN && p.upd_fused && !p.ept &&
+                  p.emb_lds && p.comp && w.edge_img &&
+                  prof_repeat("edge_step") == 1 &&
+                  (!prof_active() || (d.flags & PEMP_MPN_FUSED_FIRST_PROFILED));
+  // Serial below SIDE_MIN_E edges, when the library profiler is on (per-kernel event timing on the launch stream) or
+  // with PEMP_SERIAL_PRELUDE set.
+  p.side = E >= SIDE_MIN_E && p.steps >= 1 && !prof_active() && !serial_prelude();
+  return p;
+}
+
+// A forward's use of its launch stream's side stream: forked from the launch stream here, joined back into it (and
+// the pairing mutex released) by join() or on leaving the scope, whichever comes first -- on every exit path.
+struct SideFork {
+  SideStream* ss_;
+  const hipStream_t st_;
+  std::unique_lock<std::mutex> lock_;
+  SideFork(SideStream* ss, hipStream_t st) : ss_(ss), st_(st) {
+    if (!ss_) return;
+    lock_ = std::unique_lock<std::mutex>(ss_->mu);
+    if (hipEventRecord(ss_->fork, st_) != hipSuccess || hipStreamWaitEvent(ss_->s, ss_->fork, 0) != hipSuccess) {
+      lock_.unlock();
+      ss_ = nullptr;   // (serial then)
+    }
+  }
+  ~SideFork() { join(); }
+  hipStream_t stream() const { return ss_ ? ss_->s : st_; }
+  void join() {
+    if (!ss_) return;
+    // (a failed join is reported by the next launch check: both calls only enqueue)
+    (void)hipEventRecord(ss_->join, ss_->s);
+    (void)hipStreamWaitEvent(st_, ss_->join, 0);
+    lock_.unlock();
+    ss_ = nullptr;
+  }
+};
+
+// The launches of one forward. Every member function enqueues and returns a PEMP_* code.
+struct Forward {
+  const ForwardCall& c;
+  const ForwardPlan& p;
+  const MpnWs ws;
+  const hipStream_t st;       // the launch stream
+  hipStream_t nst;            // stream of the node kernels (the first node step may run on the side stream)
+  const int64_t* ne = nullptr;      // capacity mode: the device-side {N, E}
+  const float* node_img = nullptr;  // LDS image of the node-side MLPs
+  const float* eimg = nullptr;      // the edge-pass weight image
+  float* r_cur;               // r of the pass (R0 from the separate embedding)
+  float* r_next;
+  int rec = 0;                // recorded iterations so far
+
+  Forward(const ForwardCall& call, const ForwardPlan& plan)
+      : c(call), p(plan), ws(mpn_carve(call.workspace, plan.T, call.N, call.E, nullptr)), st(as_stream(call.stream)),
+        nst(st), r_cur(ws.EA), r_next(ws.EB) {}
+
+  bool recorded(int it) const { return it >= p.steps - p.aux - 1; }
+  bool last(int it) const { return it + 1 == p.steps; }
+
+  // what comes ahead of everything else on the launch stream: capacity mode's counts, and the two weight images
+  // where the caller did not prebuild them
+  int launch_setup() {
+    const pemp_mpn_weights& w = *c.w;
+    ne = c.cap.ne ? c.cap.ne : c.cap.n_det ? reinterpret_cast<int64_t*>(ws.err + 8) : nullptr;
+    if (c.cap.n_det && !c.cap.ne) {
+      hipLaunchKernelGGL(cap_counts_kernel, dim3(1), dim3(256), 0, st, c.cap.n_det, c.order.B, c.cap.det_cap, c.N, c.E,
+                         reinterpret_cast<int64_t*>(ws.err + 8));
+      PEMP_LAUNCH_CHECK();
+    }
+    // LDS image of the node-side MLPs: the caller's (pemp_mpn_node_image) or built here
+    node_img = w.node_img;
+    if (!node_img && (p.fused_heads || p.fused_embed)) {
+      const StagePlan plan = node_image_plan(w);
+      hipLaunchKernelGGL(stage_image_kernel, dim3((unsigned)std::min(64, (plan.total + 255) / 256)), dim3(256), 0, st,
+                         plan, ws.img);
+      PEMP_LAUNCH_CHECK();
+      node_img = ws.img;
+    }
+    // the edge-pass weight image: the caller's (pemp_mpn_edge_image, built once per weight set) or built here
+    eimg = w.edge_img;
+    if (!eimg && c.E > 0 && p.steps >= 1) {
+      EdgeImgArgs ia = edge_image_args(*c.desc, w, p.upd_fused, p.pub_head, ws.eimg);
+      hipLaunchKernelGGL(edge_image_kernel, dim3(16, (unsigned)p.T), dim3(256), 0, st, ia);
+      PEMP_LAUNCH_CHECK();
+      eimg = ws.eimg;
+    }
+    return PEMP_OK;
+  }
+
+  // the type-major edge order (unless the caller prepared it: PEMP_MPN_PREPARED)
+  int launch_order() {
+    if (c.desc->flags & PEMP_MPN_PREPARED) return PEMP_OK;
+    switch (c.order.kind) {
+      case EdgeOrder::FULLY: {
+        FullyPrepArgs fa{c.order.node_off, c.order.B, c.node_types, p.tstride, c.N, p.T, p.edge_grid,
+                         ws.seg, ws.wg_start, ws.s_src, ws.s_dst, ws.s_orig, ws.err, ne};
+        // FULLY_PARTS threads per (type, target) segment (a per-edge mapping with binary searches measured 41 us
+        // vs 15 us at C3)
+        const unsigned gx = (unsigned)std::max<int64_t>(
+            1, std::min<int64_t>(64, ((int64_t)p.T * c.order.nmax * FULLY_PARTS + 511) / 512));
+        ProfScope prof("mpn_prepare_fully", st);
+        hipLaunchKernelGGL(fully_prepare_kernel, dim3(gx, (unsigned)c.order.B), dim3(256), 0, st, fa);
+        PEMP_LAUNCH_CHECK();
+        return PEMP_OK;
+      }
+      case EdgeOrder::KNN: {
+        KnnPrepArgs ka = *c.order.knn;
+        ka.types = c.node_types; ka.ts = p.tstride; ka.N = c.N; ka.E = c.E; ka.T = p.T; ka.G = p.edge_grid;
+        ka.seg = ws.seg; ka.wg_start = ws.wg_start; ka.s_src = ws.s_src; ka.s_dst = ws.s_dst; ka.s_orig = ws.s_orig;
+        ka.err = ws.err;
+        ProfScope prof("mpn_prepare_knn", st);
+        hipLaunchKernelGGL(knn_prepare_kernel, dim3((unsigned)p.T, (unsigned)((c.N + KP_CH - 1) / KP_CH)), dim3(1024),
+                           0, st, ka);
+        PEMP_LAUNCH_CHECK();
+        return PEMP_OK;
+      }
+      case EdgeOrder::SYM: return launch_prepare_sym(c.desc, c.edge_index, c.node_types, c.N, c.E, ws, st);
+      default: return launch_prepare(c.desc, c.edge_index, c.node_types, c.N, c.E, ws, st);
+    }
+  }
+
+  // the passes' per-wave range table (static across iterations), right behind the order: its chains of dependent
+  // small loads stay off the edge embedding's workgroups
+  int launch_ranges() {
+    if (c.E == 0 || p.steps < 1) return PEMP_OK;
+    // (behind the range table's blocks: the per-edge segment positions, one edge per thread)
+    const int rg_blocks = std::min(64, (p.edge_grid * (EDGE_WAVES + 12) + 255) / 256);
+    const int pos_blocks = (int)std::min<int64_t>(1024, (c.E + 255) / 256);
+    hipLaunchKernelGGL(edge_ranges_kernel, dim3((unsigned)(rg_blocks + pos_blocks)), dim3(256), 0, st, ws.seg,
+                       ws.wg_start, ws.s_dst, p.T, c.N, p.edge_grid, ws.ranges, ne, rg_blocks);
+    PEMP_LAUNCH_CHECK();
+    return PEMP_OK;
+  }
+
+  // ---- edge embedding: its own launch writes Q0 and R0 = Q0 + W1_e_cur · e_init (edge_embed_kernel;
+  // the published shape takes the straight-line edge_embed_kernel<PREC, true>) ----
+  int launch_embed() {
+    if (p.fused_first || c.E == 0 || p.steps < 1) return PEMP_OK;
+    const pemp_mpn_desc& d = *c.desc;
+    const pemp_mpn_weights& w = *c.w;
+    const int64_t E = c.E;
+    // (the label names the fall-backs apart: `wide` and `generic`, ForwardPlan)
+    ProfScope prof(!p.emb_lds ? "edge_embed_wide" : p.emb_generic ? "edge_embed_generic" : "edge_embed", st);
+    if (p.emb_lds) {
+      // (over the edge passes' CUs: the embedding leaves the reserved CUs free too, edge_cus)
+      const int grid = (int)std::min<int64_t>((int64_t)edge_cus(E) * EMB_PER_CU,
                                               (E + 16 * EMB_WAVES - 1) / (16 * EMB_WAVES));
-      const bool fixed = embed_fixed_shape(emb_lo);
-      const bool comp = embed_composed(emb_lo, emb_prec, *w);
-      const size_t lds = (size_t)(comp ? embed_comp_floats(emb_lo) : embed_image_floats(emb_lo)) * sizeof(float);
+      const size_t lds = (size_t)(p.comp ? embed_comp_floats(p.emb_lo) : embed_image_floats(p.emb_lo)) * sizeof(float);
       // the caller's prebuilt LDS image (pemp_mpn_edge_image appends it to the edge-pass image), else staged here
-      const float* emb_img = w->edge_img ? w->edge_img + embed_image_offset(*desc, *w) : nullptr;
-#define PEMP_EMBED_LAUNCH(P, FX)                                                                                   \
-  hipLaunchKernelGGL((edge_embed_kernel<P, FX>), dim3(grid), dim3(64 * EMB_WAVES), lds, pst, w->edge_emb, emb_lo,   \
-                     w->emb_bf, edge_attr, desc->edge_attr_dim, ws.s_orig, E, w->q0_w, w->q0_b, w->e1_w, w->e1_bf, \
-                     ws.EA, ws.Q0, ne, emb_img, w->emb_comp_bf, w->emb_comp_b)
-      if (emb_prec == PEMP_PREC_F16X3) {
-        if (comp) PEMP_EMBED_LAUNCH(2, 2);
-        else if (fixed) PEMP_EMBED_LAUNCH(2, 1);
-        else PEMP_EMBED_LAUNCH(2, 0);
-      } else if (emb_prec == PEMP_PREC_BF16X3) {
-        if (fixed) PEMP_EMBED_LAUNCH(1, 1);
-        else PEMP_EMBED_LAUNCH(1, 0);
-      } else
-        PEMP_EMBED_LAUNCH(0, 0);
-#undef PEMP_EMBED_LAUNCH
+      const float* emb_img = w.edge_img ? w.edge_img + embed_image_offset(d, w) : nullptr;
+      // (fp32 embeds only as <0, 0>, and only f16x3 has the composed form <2, 2>)
+      with_prec(p.emb_prec, [&](auto P) {
+        constexpr int PREC = decltype(P)::value;
+        auto launch = [&](auto FX) {
+          hipLaunchKernelGGL((edge_embed_kernel<PREC, decltype(FX)::value>), dim3(grid), dim3(64 * EMB_WAVES), lds, st,
+                             w.edge_emb, p.emb_lo, w.emb_bf, c.edge_attr, d.edge_attr_dim, ws.s_orig, E, w.q0_w, w.q0_b,
+                             w.e1_w, w.e1_bf, ws.EA, ws.Q0, ne, emb_img, w.emb_comp_bf, w.emb_comp_b);
+        };
+        if constexpr (PREC == PEMP_PREC_F16X3)
+          if (p.comp) return launch(std::integral_constant<int, 2>{});
+        if constexpr (PREC != PEMP_PREC_FP32)
+          if (p.fixed) return launch(std::integral_constant<int, 1>{});
+        launch(std::integral_constant<int, 0>{});
+      });
     } else {
-      hipLaunchKernelGGL(edge_embed_wide_kernel, dim3((unsigned)((E + 63) / 64)), dim3(256), 0, pst, w->edge_emb,
-                         edge_attr, desc->edge_attr_dim, ws.s_orig, E, w->q0_w, w->q0_b, w->e1_w, ws.EA, ws.Q0,
-                         desc->precision == PEMP_PREC_F16X3 ? dom<2>() : 1.0f);
+      hipLaunchKernelGGL(edge_embed_wide_kernel, dim3((unsigned)((E + 63) / 64)), dim3(256), 0, st, w.edge_emb,
+                         c.edge_attr, d.edge_attr_dim, ws.s_orig, E, w.q0_w, w.q0_b, w.e1_w, ws.EA, ws.Q0,
+                         d.precision == PEMP_PREC_F16X3 ? dom<2>() : 1.0f);
     }
     PEMP_LAUNCH_CHECK();
+    return PEMP_OK;
   }
-  return PEMP_OK;
-  };
 
-  // ---- iterations ----
-  const int NO = 128 + 64 * T;
-  const bool fused_heads = mlp_ok(w->node_head, 64, 64) && mlp_ok(w->class_head, 64, 64);
-  const unsigned node_grid = (unsigned)((N + 15) / 16);
-  const int table_prec = desc->precision != PEMP_PREC_FP32 && w->pre_bf ? desc->precision : PEMP_PREC_FP32;
-  const int table_groups = (NO / 16 + 3) / 4;
-  const unsigned table_grid = (unsigned)(((N + 16 * TBL_TILES - 1) / (16 * TBL_TILES)) * table_groups);
   // x for the next stage (mode) + heads when slot >= 0, then the node table when `table`
-  // middle steps of the attention model (update block in the edge pass, no heads): the node update runs inside the
-  // node-table launch (node_table_kernel<PREC, 1, true>) instead of a launch of its own
-  const unsigned table_grid1 = (unsigned)(((N + 15) / 16) * table_groups);
-  hipStream_t nst = st;   // stream of the node kernels (the first node step runs on the prelude side stream)
-  auto node_step = [&](int mode, bool table, int slot, bool dup) -> int {
-    // (every column group re-reads the tile's aggregates: worth it while those re-reads stay small -- C2 -- not at
-    // C3, where they are ~100 MB per call and the fused launch only ties the two it replaces. Round 6: a wide form,
-    // 16 waves = 256 columns per workgroup so a tile's aggregates are summed 5 instead of 19 times, took 24 us per
-    // call against 8 + 10 us for the two launches at c3 / c3knn10 (profiles/r06_node_sum_wide.md); not kept.)
-    if (mode == ROWS_SUM && table && slot < 0 && !ept && NODE_SUM_TABLE &&
-        N * T * 256 * (int64_t)table_groups <= (int64_t)NODE_SUM_TABLE_MAX_MB << 20) {
-      NodeTableArgs ta{ws.X, N, w->pre_w, w->pre_b, w->pre_bf, NO, table_groups, ws.NT, ne, ws.agg, ws.seg, T,
-                       w->upd_b};
+  int node_step(int mode, bool table, int slot, bool dup) {
+    const pemp_mpn_weights& w = *c.w;
+    const int64_t N = c.N;
+    const int T = p.T, J = p.J;
+    // middle steps of the attention model (update block in the edge pass, no heads): the node update runs inside the
+    // node-table launch (node_table_kernel<PREC, 1, true>) instead of a launch of its own
+    if (mode == ROWS_SUM && table && slot < 0 && p.sum_in_table) {
+      NodeTableArgs ta{ws.X, N, w.pre_w, w.pre_b, w.pre_bf, p.NO, p.table_groups, ws.NT, ne, ws.agg, ws.seg, T,
+                       w.upd_b};
       ProfScope prof("node_update_table", nst);
-      if (table_prec == PEMP_PREC_F16X3)
-        hipLaunchKernelGGL((node_table_kernel<2, 1, true>), dim3(table_grid1), dim3(256), 0, nst, ta);
-      else if (table_prec == PEMP_PREC_BF16X3)
-        hipLaunchKernelGGL((node_table_kernel<1, 1, true>), dim3(table_grid1), dim3(256), 0, nst, ta);
-      else
-        hipLaunchKernelGGL((node_table_kernel<0, 1, true>), dim3(table_grid1), dim3(256), 0, nst, ta);
+      with_prec(p.table_prec, [&](auto P) {
+        hipLaunchKernelGGL((node_table_kernel<decltype(P)::value, 1, true>), dim3(p.table_grid1), dim3(256), 0, nst, ta);
+      });
       PEMP_LAUNCH_CHECK();
       return PEMP_OK;
     }
-    if (mode == -1 && w->upd_mlp.n_layers > 0) {     // hierarchical update MLP (dense-folded)
-      NodeMlpArgs ma{ws.agg, ws.seg, T, N, w->upd_mlp, nmlp_max_out(w->upd_mlp), ws.X, ne};
+    if (mode == NODE_UPDATE_MLP && w.upd_mlp.n_layers > 0) {   // hierarchical update MLP (dense-folded)
+      NodeMlpArgs ma{ws.agg, ws.seg, T, N, w.upd_mlp, nmlp_max_out(w.upd_mlp), ws.X, ne};
       ProfScope prof("node_update", nst);
-      hipLaunchKernelGGL(node_mlp_kernel, dim3(node_grid), dim3(256), nmlp_lds_bytes(T, w->upd_mlp), nst, ma);
+      hipLaunchKernelGGL(node_mlp_kernel, dim3(p.node_grid), dim3(256), nmlp_lds_bytes(T, w.upd_mlp), nst, ma);
       PEMP_LAUNCH_CHECK();
       mode = ROWS_NONE;
-    } else if (mode == -1) {                           // update MLP on non-linear aggregates
-      NodeUpdateArgs ua{ws.agg, ws.seg, T, N, w->upd_w, w->upd_b, ws.X, ne};
+    } else if (mode == NODE_UPDATE_MLP) {                      // update MLP on non-linear aggregates
+      NodeUpdateArgs ua{ws.agg, ws.seg, T, N, w.upd_w, w.upd_b, ws.X, ne};
       ProfScope prof("node_update", nst);
-      hipLaunchKernelGGL(node_update_kernel, dim3(node_grid, 4), dim3(64 * UPD_WAVES), 0, nst, ua);
+      hipLaunchKernelGGL(node_update_kernel, dim3(p.node_grid, 4), dim3(64 * UPD_WAVES), 0, nst, ua);
       PEMP_LAUNCH_CHECK();
       mode = ROWS_NONE;
     }
     NodeRowsArgs na{};
     na.mode = mode;
-    if (mode == ROWS_EMBED) { na.x_in = x; na.in_ld = desc->node_in_dim; }
-    na.agg = ws.agg; na.seg = ws.seg; na.T = T; na.upd_b = w->upd_b; na.N = N; na.X = ws.X;
-    na.node_head = w->node_head; na.class_head = w->class_head; na.J = J;
+    if (mode == ROWS_EMBED) { na.x_in = c.x; na.in_ld = c.desc->node_in_dim; }
+    na.agg = ws.agg; na.seg = ws.seg; na.T = T; na.upd_b = w.upd_b; na.N = N; na.X = ws.X;
+    na.node_head = w.node_head; na.class_head = w.class_head; na.J = J;
     na.ne = ne;
-    if (slot >= 0 && fused_heads && ne) {   // capacity mode: bases, the kernel places rows slot (+ 1) of its N
-      na.node_out = node_logits;
-      na.class_out = class_logits;
+    if (slot >= 0 && p.fused_heads && ne) {   // capacity mode: bases, the kernel places rows slot (+ 1) of its N
+      na.node_out = c.node_logits;
+      na.class_out = c.class_logits;
       na.slot = slot;
       na.dup = dup ? 1 : 0;
-    } else if (slot >= 0 && fused_heads) {
-      na.node_out = node_logits + (int64_t)slot * N;
-      na.class_out = class_logits + (int64_t)slot * N * J;
+    } else if (slot >= 0 && p.fused_heads) {
+      na.node_out = c.node_logits + (int64_t)slot * N;
+      na.class_out = c.class_logits + (int64_t)slot * N * J;
       na.node_out2 = dup ? na.node_out + N : nullptr;
       na.class_out2 = dup ? na.class_out + N * J : nullptr;
     }
-    na.emb = w->node_emb;
+    na.emb = w.node_emb;
     na.img = node_img;
-    na.head_off = fused_embed_ ? mlp_lds_floats(w->node_emb) : 0;
-    na.head_floats = mlp_lds_floats(w->node_head) + mlp_lds_floats(w->class_head);
-    na.emb_whole = mode == ROWS_EMBED && node_emb_whole(w->node_emb);
+    na.head_off = p.fused_embed ? mlp_lds_floats(w.node_emb) : 0;
+    na.head_floats = mlp_lds_floats(w.node_head) + mlp_lds_floats(w.class_head);
+    na.emb_whole = mode == ROWS_EMBED && node_emb_whole(w.node_emb);
     if (na.mode != ROWS_NONE || na.node_out) {
       ProfScope prof(mode == ROWS_EMBED ? "node_embed" : "node_update", nst);
-      hipLaunchKernelGGL(node_rows_kernel, dim3(node_grid), dim3(256), node_rows_lds_bytes(na), nst, na);
+      hipLaunchKernelGGL(node_rows_kernel, dim3(p.node_grid), dim3(256), node_rows_lds_bytes(na), nst, na);
       PEMP_LAUNCH_CHECK();
     }
-    if (slot >= 0 && !fused_heads) {
+    if (slot >= 0 && !p.fused_heads) {
       for (int k = 0; k < (dup ? 2 : 1); ++k) {
         int r2;
-        if ((r2 = rows_mlp("heads", w->node_head, ws.X + 64, 128, N, node_logits + (int64_t)(slot + k) * N, 1, nullptr, 0, nst)))
+        if ((r2 = rows_mlp("heads", w.node_head, ws.X + 64, 128, N, c.node_logits + (int64_t)(slot + k) * N, 1, nullptr,
+                           0, nst)))
           return r2;
-        if ((r2 = rows_mlp("heads", w->class_head, ws.X + 64, 128, N, class_logits + (int64_t)(slot + k) * N * J, J,
+        if ((r2 = rows_mlp("heads", w.class_head, ws.X + 64, 128, N, c.class_logits + (int64_t)(slot + k) * N * J, J,
                            nullptr, 0, nst)))
           return r2;
       }
     }
     if (table) {
-      NodeTableArgs ta{ws.X, N, w->pre_w, w->pre_b, w->pre_bf, NO, table_groups, ws.NT, ne};
+      NodeTableArgs ta{ws.X, N, w.pre_w, w.pre_b, w.pre_bf, p.NO, p.table_groups, ws.NT, ne};
       ProfScope prof("node_table", nst);
-      if (table_prec == PEMP_PREC_F16X3)
-        hipLaunchKernelGGL(node_table_kernel<2>, dim3(table_grid), dim3(256), 0, nst, ta);
-      else if (table_prec == PEMP_PREC_BF16X3)
-        hipLaunchKernelGGL(node_table_kernel<1>, dim3(table_grid), dim3(256), 0, nst, ta);
-      else
-        hipLaunchKernelGGL(node_table_kernel<0>, dim3(table_grid), dim3(256), 0, nst, ta);
+      with_prec(p.table_prec, [&](auto P) {
+        hipLaunchKernelGGL(node_table_kernel<decltype(P)::value>, dim3(p.table_grid), dim3(256), 0, nst, ta);
+      });
       PEMP_LAUNCH_CHECK();
-      if (ept) {   // columns 0..127 of the table: the per-type node terms (zero rows in pre_w)
-        NodeEptArgs xa{ws.X, node_types, tstride, T, N, w->ept_l1_w, w->ept_l1_b, w->ept_l2_w, w->ept_l2_b,
-                       w->ept_o1_w, w->ept_o2_w, ws.NT, NO,
-                       desc->precision == PEMP_PREC_F16X3 ? dom<2>() : 1.0f, ne};
-        hipLaunchKernelGGL(node_ept_kernel, dim3(node_grid), dim3(256), 0, nst, xa);
+      if (p.ept) {   // columns 0..127 of the table: the per-type node terms (zero rows in pre_w)
+        NodeEptArgs xa{ws.X, c.node_types, p.tstride, T, N, w.ept_l1_w, w.ept_l1_b, w.ept_l2_w, w.ept_l2_b,
+                       w.ept_o1_w, w.ept_o2_w, ws.NT, p.NO,
+                       c.desc->precision == PEMP_PREC_F16X3 ? dom<2>() : 1.0f, ne};
+        hipLaunchKernelGGL(node_ept_kernel, dim3(p.node_grid), dim3(256), 0, nst, xa);
         PEMP_LAUNCH_CHECK();
       }
     }
     return PEMP_OK;
-  };
-  // node embedding + node table of the first iteration (or, without iterations, the heads on the
-  // embedding); embedding widths > 128 would not fit the node step's LDS rows: separate launch
-  const bool fused_embed = fused_embed_;
-  // The edge prelude (prepare, wave ranges, edge embedding) needs nothing the node embedding and the first
-  // node table produce: it runs on a side stream (forked from and joined back into `st`) while they run
-  // here (their 16-row grids leave most CUs idle). Serial below PEMP_SIDE_MIN_E edges, when the library
-  // profiler is on (per-kernel event timing on `st`) or with PEMP_SERIAL_PRELUDE set.
-  SideStream* ss = (E >= PEMP_SIDE_MIN_E && steps >= 1 && !prof_active() && !serial_prelude()) ? side_stream_for(st)
-                                                                                                  : nullptr;
-  std::unique_lock<std::mutex> side_lock;
-  if (ss) {
-    side_lock = std::unique_lock<std::mutex>(ss->mu);
-    if (hipEventRecord(ss->fork, st) != hipSuccess || hipStreamWaitEvent(ss->s, ss->fork, 0) != hipSuccess) {
-      side_lock.unlock();
-      ss = nullptr;
-    } else {
-      pst = ss->s;
-    }
   }
-  auto join_side = [&]() {
-    if (!ss) return;
-    // (a failed join is reported by the next launch check: both calls only enqueue)
-    (void)hipEventRecord(ss->join, ss->s);
-    (void)hipStreamWaitEvent(st, ss->join, 0);
-    side_lock.unlock();
-    ss = nullptr;
-  };
-  // PEMP_NODE_ON_SIDE (round 6, the default): the node embedding + first node table go to the side stream and the
-  // edge prelude (order, ranges, embedding) stays on the launch stream, so the step's critical path -- graph build ->
-  // order -> ranges -> embedding -> first pass -- carries neither the fork's nor the join's cross-stream wait (the
-  // side chain, ~20 us, is done long before the ~60 us prelude). Otherwise: the order and the range table on the side
-  // stream, the node kernels here, and the edge embedding placed as below.
-  if (ss && PEMP_NODE_ON_SIDE) {
-    nst = ss->s;
-    pst = st;
-    if (!fused_embed) {
-      if ((rc = rows_mlp("node_embed", w->node_emb, x, desc->node_in_dim, N, ws.X, 128, ws.X + 64, 128, nst))) {
-        nst = st;
-        join_side();
-        return rc;
-      }
-    }
-    rc = node_step(fused_embed ? ROWS_EMBED : ROWS_NONE, steps > 0, steps > 0 ? -1 : 0, false);
-    nst = st;
-    if (rc || (rc = edge_prepare()) || (rc = edge_embed())) { join_side(); return rc; }
-    join_side();
-  } else {
-  // side stream: the edge order and the edge passes' range table behind it; meanwhile the node embedding + first
-  // node table here (short kernels with 16-row grids); then, joined, the edge embedding (every CU, all of its LDS)
-  if (ss && (rc = edge_prepare())) { join_side(); return rc; }
-  if (!fused_embed) {
-    if ((rc = rows_mlp("node_embed", w->node_emb, x, desc->node_in_dim, N, ws.X, 128, ws.X + 64, 128, st))) {
-      join_side();
-      return rc;
-    }
-  }
-  if ((rc = node_step(fused_embed ? ROWS_EMBED : ROWS_NONE, steps > 0, steps > 0 ? -1 : 0, false))) {
-    join_side();
-    return rc;
-  }
-  // the edge embedding on the launch stream once the order is ready: the join's wait resolves behind the node
-  // kernels (a join after the embedding waited ~13 us for the cross-stream event, measured). Inside a captured
-  // capacity-mode forward the join is a graph edge, not an event wait: there the embedding stays on the side
-  // stream, right behind the order, concurrent with the node embedding and first table (EMBED_ON_SIDE)
-  if (ss && cap_ndet && EMBED_ON_SIDE) {
-    if ((rc = edge_embed())) { join_side(); return rc; }
-    join_side();
-    pst = st;
-  } else if (ss) {
-    pst = st;
-    join_side();
-    if ((rc = edge_embed())) return rc;
-  } else if ((rc = edge_prepare()) || (rc = edge_embed())) {
-    return rc;
-  }
-  }
-  float* e_cur = ws.EA;                           // r of the pass (R0 from the separate embedding)
-  float* e_nxt = ws.EB;
-  int rec = 0;
-  for (int it = 0; it < steps; ++it) {
-    const bool record = it >= steps - aux - 1;
-    const bool last = it + 1 == steps;
-    if (E > 0) {
-      EdgeStepArgs ea{};
-      ea.N = N; ea.E = E; ea.T = T; ea.t_nt_ld = NO;
-      const bool pub = record && pub_head;         // the published head's weights ride in the LDS image
-      // (12-wave table: recorded middle passes with the published head; every other pass runs 16 waves)
-      ea.ranges = ws.ranges + (pub && !last ? (int64_t)edge_grid * EDGE_WAVES : 0);
-      ea.s_src = ws.s_src; ea.s_dst = ws.s_dst; ea.s_orig = ws.s_orig;
-      const int stage = (last ? STAGE_LAST : STAGE_MID) | (ept ? STAGE_EPT : 0);
-      ea.NT = ws.NT; ea.Q0 = ws.Q0; ea.r_cur = e_cur; ea.r_next = e_nxt;
-      ea.img = eimg; ea.img_stride = img_stride(upd_fused, pub_head);
-      ea.agg = ws.agg; ea.head = w->edge_head;
-      ea.edge_logits = record ? (ne ? edge_logits : edge_logits + (int64_t)rec * E) : nullptr;
-      ea.ne = ne;
-      ea.rec = rec;
-      ea.write_next = !last;
+
+  // the edge pass of iteration `it`: reads r_cur / NT / Q0, writes r_next / agg / (recorded) the edge logits
+  int edge_pass(int it) {
+    const pemp_mpn_desc& d = *c.desc;
+    const bool record = recorded(it), is_last = last(it);
+    EdgeStepArgs ea{};
+    ea.N = c.N; ea.E = c.E; ea.T = p.T; ea.t_nt_ld = p.NO;
+    const bool pub = record && p.pub_head;         // the published head's weights ride in the LDS image
+    // (12-wave table: recorded middle passes with the published head; every other pass runs 16 waves)
+    ea.ranges = ws.ranges + (pub && !is_last ? (int64_t)p.edge_grid * EDGE_WAVES : 0);
+    ea.s_src = ws.s_src; ea.s_dst = ws.s_dst; ea.s_orig = ws.s_orig;
+    const int stage = (is_last ? STAGE_LAST : STAGE_MID) | (p.ept ? STAGE_EPT : 0);
+    ea.NT = ws.NT; ea.Q0 = ws.Q0; ea.r_cur = r_cur; ea.r_next = r_next;
+    ea.img = eimg; ea.img_stride = img_stride(p.upd_fused, p.pub_head);
+    ea.agg = ws.agg; ea.head = c.w->edge_head;
+    ea.edge_logits = record ? (ne ? c.edge_logits : c.edge_logits + (int64_t)rec * c.E) : nullptr;
+    ea.ne = ne;
+    ea.rec = rec;
+    ea.write_next = !is_last;
 #ifdef PEMP_STAMPS
-      ea.stamps = it == g_diag_stamp_pass ? g_diag_stamps : nullptr;
+    ea.stamps = it == g_diag_stamp_pass ? g_diag_stamps : nullptr;
 #endif
-      if (it == 0 && fused_first) {   // embedding + pass 0 in one launch (the side stream has joined: it reads NT)
-        ea.ea = edge_attr; ea.A = desc->edge_attr_dim;
-        ea.emb_img = w->edge_img + embed_image_offset(*desc, *w);
-        ProfScope prof("edge_first", st);
-        hipLaunchKernelGGL((edge_step_kernel<PEMP_AGGR_ATTN, 0, 2, 1, STAGE_MID | STAGE_FIRST>), dim3(edge_grid),
-                           dim3(64 * EDGE_WAVES), 0, st, ea);
-        PEMP_LAUNCH_CHECK();
-      } else {
-      const char* label = !record ? "edge_step" : pub ? "edge_step_head" : "edge_step_head_generic";
-      ProfScope prof(label, st);
-      // a pass is idempotent (reads r_cur / NT / Q0, rewrites r_next / agg / logits), so the profiler
-      // may repeat it between one event pair ("edge_step@R")
-      for (int rep = prof_repeat(label); rep > 0; --rep) {
-        switch (desc->aggr) {
-          case PEMP_AGGR_ATTN: launch_edge_step<PEMP_AGGR_ATTN>(ea, record, pub, edge_grid, desc->precision, upd_fused, stage, st); break;
-          case PEMP_AGGR_SUM: launch_edge_step<PEMP_AGGR_SUM>(ea, record, pub, edge_grid, desc->precision, upd_fused, stage, st); break;
-          case PEMP_AGGR_MEAN: launch_edge_step<PEMP_AGGR_MEAN>(ea, record, pub, edge_grid, desc->precision, upd_fused, stage, st); break;
-          default: launch_edge_step<PEMP_AGGR_MAX>(ea, record, pub, edge_grid, desc->precision, false, stage, st); break;
-        }
-        PEMP_LAUNCH_CHECK();
-      }
-      }
+    if (it == 0 && p.fused_first) {   // embedding + pass 0 in one launch (the side stream has joined: it reads NT)
+      ea.ea = c.edge_attr; ea.A = d.edge_attr_dim;
+      ea.emb_img = c.w->edge_img + embed_image_offset(d, *c.w);
+      ProfScope prof("edge_first", st);
+      hipLaunchKernelGGL((edge_step_kernel<PEMP_AGGR_ATTN, 0, 2, 1, STAGE_MID | STAGE_FIRST>), dim3(p.edge_grid),
+                         dim3(64 * EDGE_WAVES), 0, st, ea);
+      PEMP_LAUNCH_CHECK();
+      return PEMP_OK;
     }
-    // node update + next node table; heads when recorded (the last iteration's heads also fill
-    // the post-loop slot: NODE_STEPS = 0 leaves x unchanged, NodeClassificationMPNSimple.py:93-94)
-    const int mode = upd_fused ? ROWS_SUM : (w->upd_w || w->upd_mlp.n_layers > 0) ? -1 : ROWS_COPY;
-    if ((rc = node_step(mode, !last, record ? rec : -1, last))) return rc;
-    if (record) ++rec;
-    float* tmp = e_cur; e_cur = e_nxt; e_nxt = tmp;
+    const char* label = !record ? "edge_step" : pub ? "edge_step_head" : "edge_step_head_generic";
+    ProfScope prof(label, st);
+    // a pass is idempotent (reads r_cur / NT / Q0, rewrites r_next / agg / logits), so the profiler
+    // may repeat it between one event pair ("edge_step@R")
+    for (int rep = prof_repeat(label); rep > 0; --rep) {
+      switch (d.aggr) {
+        case PEMP_AGGR_ATTN: launch_edge_step<PEMP_AGGR_ATTN>(ea, record, pub, p.edge_grid, d.precision, p.upd_fused, stage, st); break;
+        case PEMP_AGGR_SUM: launch_edge_step<PEMP_AGGR_SUM>(ea, record, pub, p.edge_grid, d.precision, p.upd_fused, stage, st); break;
+        case PEMP_AGGR_MEAN: launch_edge_step<PEMP_AGGR_MEAN>(ea, record, pub, p.edge_grid, d.precision, p.upd_fused, stage, st); break;
+        default: launch_edge_step<PEMP_AGGR_MAX>(ea, record, pub, p.edge_grid, d.precision, false, stage, st); break;
+      }
+      PEMP_LAUNCH_CHECK();
+    }
+    return PEMP_OK;
   }
-  return PEMP_OK;
+
+  // The prelude. The edge prelude (order, wave ranges, edge embedding) needs nothing the node embedding and the first
+  // node table produce (their 16-row grids leave most CUs idle). From SIDE_MIN_E edges on (ForwardPlan::side) those
+  // two go to a side stream, forked from and joined back into the launch stream, and the edge prelude stays on the
+  // launch stream: the step's critical path -- graph build -> order -> ranges -> embedding -> first pass -- then
+  // carries neither the fork's nor the join's cross-stream wait (the side chain, ~20 us, is done long before the
+  // ~60 us prelude). Without a side stream the same launches go to the launch stream in the same order.
+  int prelude() {
+    int rc;
+    SideFork side(p.side ? side_stream_for(st) : nullptr, st);
+    nst = side.stream();
+    // node embedding + node table of the first iteration (or, without iterations, the heads on the embedding);
+    // embedding widths > 128 would not fit the node step's LDS rows: separate launch
+    rc = p.fused_embed ? PEMP_OK
+                       : rows_mlp("node_embed", c.w->node_emb, c.x, c.desc->node_in_dim, c.N, ws.X, 128, ws.X + 64, 128, nst);
+    if (!rc) rc = node_step(p.fused_embed ? ROWS_EMBED : ROWS_NONE, p.steps > 0, p.steps > 0 ? -1 : 0, false);
+    nst = st;
+    if (!rc && !(rc = launch_order()) && !(rc = launch_ranges())) rc = launch_embed();
+    return rc;   // (leaving the scope joins the side stream, on the error paths too)
+  }
+
+  int run() {
+    int rc;
+    if ((rc = launch_setup()) || (rc = prelude())) return rc;
+    for (int it = 0; it < p.steps; ++it) {
+      if (c.E > 0 && (rc = edge_pass(it))) return rc;
+      // node update + next node table; heads when recorded (the last iteration's heads also fill
+      // the post-loop slot: NODE_STEPS = 0 leaves x unchanged, NodeClassificationMPNSimple.py:93-94)
+      if ((rc = node_step(p.node_mode, !last(it), recorded(it) ? rec : -1, last(it)))) return rc;
+      if (recorded(it)) ++rec;
+      std::swap(r_cur, r_next);
+    }
+    return PEMP_OK;
+  }
+};
+
+// One inference forward: every C entry point below fills a ForwardCall and ends here.
+static int mpn_forward(const ForwardCall& c) {
+  if (const int rc = check_forward_args(c)) return rc;
+  if (c.N == 0) return PEMP_OK;   // (with or without edges: nothing is launched or written)
+  const ForwardPlan p = plan_forward(c);
+  return Forward(c, p).run();
 }
 
 extern "C" int pemp_mpn_forward(const pemp_mpn_desc* desc, const pemp_mpn_weights* w, const float* x,
                                 const float* edge_attr, const int64_t* edge_index, const int64_t* node_types,
                                 int64_t N, int64_t E, float* edge_logits, float* node_logits, float* class_logits,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-  return mpn_forward_impl(desc, w, x, edge_attr, edge_index, node_types, N, E, edge_logits, node_logits, class_logits,
-                          workspace, workspace_bytes, stream, nullptr, 0, 0);
+  ForwardCall c{};
+  c.desc = desc; c.w = w; c.x = x; c.edge_attr = edge_attr; c.edge_index = edge_index; c.node_types = node_types;
+  c.N = N; c.E = E; c.edge_logits = edge_logits; c.node_logits = node_logits; c.class_logits = class_logits;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  return mpn_forward(c);
 }
 
 extern "C" int pemp_mpn_forward_fully(const pemp_mpn_desc* desc, const pemp_mpn_weights* w, const float* x,
@@ -4526,11 +4503,14 @@ extern "C" int pemp_mpn_forward_fully(const pemp_mpn_desc* desc, const pemp_mpn_
   }
   PEMP_CHECK_ARG(e_full == E, "pemp_mpn_forward_fully: E=%lld is not the fully graph's %lld", (long long)E,
                  (long long)e_full);
-  if (nmax > FULLY_MAXN)   // closed-form lists live in LDS: larger images take the sorting prepare
-    return mpn_forward_impl(desc, w, x, edge_attr, edge_index, node_types, N, E, edge_logits, node_logits,
-                            class_logits, workspace, workspace_bytes, stream, nullptr, 0, 0);
-  return mpn_forward_impl(desc, w, x, edge_attr, edge_index, node_types, N, E, edge_logits, node_logits, class_logits,
-                          workspace, workspace_bytes, stream, node_off, B, (int)nmax);
+  ForwardCall c{};
+  c.desc = desc; c.w = w; c.x = x; c.edge_attr = edge_attr; c.edge_index = edge_index; c.node_types = node_types;
+  c.N = N; c.E = E; c.edge_logits = edge_logits; c.node_logits = node_logits; c.class_logits = class_logits;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  if (nmax <= FULLY_MAXN) {   // closed-form lists live in LDS: larger images take the sorting prepare
+    c.order.kind = EdgeOrder::FULLY; c.order.node_off = node_off; c.order.B = B; c.order.nmax = (int)nmax;
+  }
+  return mpn_forward(c);
 }
 
 // ---- HIP graphs of the capacity-mode forward ------------------------------------------------------------------
@@ -4584,16 +4564,6 @@ static GraphStream* graph_stream(int dev) {
   return g;
 }
 
-static int cap_forward_direct(const pemp_mpn_desc* desc, const pemp_mpn_weights* w, const float* x,
-                              const float* edge_attr, const int64_t* node_types, int64_t n_cap, int64_t e_cap,
-                              const int32_t* n_det, int det_cap, const int64_t* node_off, int B, float* edge_logits,
-                              float* node_logits, float* class_logits, void* workspace, size_t workspace_bytes,
-                              void* stream) {
-  return mpn_forward_impl(desc, w, x, edge_attr, nullptr, node_types, n_cap, e_cap, edge_logits, node_logits,
-                          class_logits, workspace, workspace_bytes, stream, node_off, B, det_cap, false, n_det,
-                          det_cap, nullptr, (desc->flags & PEMP_MPN_COUNTS_IN_OFFSETS) ? node_off + B + 1 : nullptr);
-}
-
 // Graph statistics for the tests (pemp_mpn_graph_stats): captures made, replays launched, captures refused.
 static std::atomic<uint64_t> g_graph_captures{0}, g_graph_replays{0}, g_graph_refused{0};
 
@@ -4612,7 +4582,7 @@ extern "C" int pemp_edge_cus_policy(int num_cus_, int64_t E, int reserve_request
   PEMP_CHECK_ARG(num_cus_ >= 1 && E >= 0, "pemp_edge_cus_policy: bad args");
   if (reserve_request < 0) {
     const char* e = getenv("PEMP_RESERVE_CUS");
-    reserve_request = e ? atoi(e) : PEMP_RESERVE_CUS_DEFAULT;
+    reserve_request = e ? atoi(e) : RESERVE_CUS_DEFAULT;
   }
   return edge_cus_policy(num_cus_, E, reserve_request);
 }
@@ -4632,14 +4602,21 @@ extern "C" int pemp_mpn_forward_fully_cap(const pemp_mpn_desc* desc, const pemp_
                                           void* workspace, size_t workspace_bytes, void* stream) {
   PEMP_CHECK_ARG(desc && w && n_det && node_off && B >= 1 && B <= FULLY_MAXB, "pemp_mpn_forward_fully_cap: bad args");
   PEMP_CHECK_ARG(n_cap >= 1 && e_cap >= 0 && det_cap >= 1, "pemp_mpn_forward_fully_cap: bad capacities");
-  if (det_cap > FULLY_MAXN || !node_heads_fused(*w) || !node_embed_fused(*w) || !mlp_ok(w->edge_emb, 64, 64) ||
-      !(mlp_ok(w->node_head, 64, 64) && mlp_ok(w->class_head, 64, 64))) {
+  if (det_cap > FULLY_MAXN || !node_heads_fused(*w) || !node_embed_fused(*w) || !mlp_ok(w->edge_emb, 64, 64)) {
     set_error("pemp_mpn_forward_fully_cap: this model / capacity takes the exact forward");
     return PEMP_ERR_UNSUPPORTED;
   }
+  // the forward's own launches on stream `s`: N and E are the capacities, the closed-form order takes det_cap as
+  // the bound of an image's nodes
   auto direct = [&](void* s) {
-    return cap_forward_direct(desc, w, x, edge_attr, node_types, n_cap, e_cap, n_det, det_cap, node_off, B,
-                              edge_logits, node_logits, class_logits, workspace, workspace_bytes, s);
+    ForwardCall c{};
+    c.desc = desc; c.w = w; c.x = x; c.edge_attr = edge_attr; c.node_types = node_types;
+    c.N = n_cap; c.E = e_cap; c.edge_logits = edge_logits; c.node_logits = node_logits; c.class_logits = class_logits;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = s;
+    c.order.kind = EdgeOrder::FULLY; c.order.node_off = node_off; c.order.B = B; c.order.nmax = det_cap;
+    c.cap.n_det = n_det; c.cap.det_cap = det_cap;
+    c.cap.ne = (desc->flags & PEMP_MPN_COUNTS_IN_OFFSETS) ? node_off + B + 1 : nullptr;
+    return mpn_forward(c);
   };
   // PEMP_DEBUG_SYNC synchronises the device after every launch, which a capturing stream does not allow
   if (graphs_off() || prof_active() || debug_sync()) return direct(stream);
@@ -4744,9 +4721,13 @@ extern "C" int pemp_mpn_forward_sym(const pemp_mpn_desc* desc, const pemp_mpn_we
                                     const float* edge_attr, const int64_t* edge_index, const int64_t* node_types,
                                     int64_t N, int64_t E, float* edge_logits, float* node_logits, float* class_logits,
                                     void* workspace, size_t workspace_bytes, void* stream) {
+  ForwardCall c{};
+  c.desc = desc; c.w = w; c.x = x; c.edge_attr = edge_attr; c.edge_index = edge_index; c.node_types = node_types;
+  c.N = N; c.E = E; c.edge_logits = edge_logits; c.node_logits = node_logits; c.class_logits = class_logits;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
   // the packed row entries hold a node id in SYM_TBITS bits: larger graphs take the sorting prepare
-  return mpn_forward_impl(desc, w, x, edge_attr, edge_index, node_types, N, E, edge_logits, node_logits, class_logits,
-                          workspace, workspace_bytes, stream, nullptr, 0, 0, N < (1ll << SYM_TBITS));
+  if (N < (1ll << SYM_TBITS)) c.order.kind = EdgeOrder::SYM;
+  return mpn_forward(c);
 }
 
 extern "C" int pemp_mpn_forward_knn(const pemp_mpn_desc* desc, const pemp_mpn_weights* w, const float* x,
@@ -4764,14 +4745,15 @@ extern "C" int pemp_mpn_forward_knn(const pemp_mpn_desc* desc, const pemp_mpn_we
                    "pemp_mpn_forward_knn: image %d holds more than %d nodes", b, 64 * KP_W);
   KnnPrepArgs ka{};
   ka.R = static_cast<const unsigned long long*>(knn_rows);
-  ka.rowstart = knn_rowstart;
-  ka.node_off = node_off;
-  ka.ecount = ecount;
-  ka.B = B;
+  ka.rowstart = knn_rowstart; ka.node_off = node_off; ka.ecount = ecount; ka.B = B;
   const char* cap = getenv("PEMP_KNN_LIST_CAP");
   ka.list_cap = cap ? std::max(0, std::min(KP_LIST, atoi(cap))) : KP_LIST;
-  return mpn_forward_impl(desc, w, x, edge_attr, edge_index, node_types, N, E, edge_logits, node_logits, class_logits,
-                          workspace, workspace_bytes, stream, nullptr, 0, 0, false, nullptr, 0, &ka);
+  ForwardCall c{};
+  c.desc = desc; c.w = w; c.x = x; c.edge_attr = edge_attr; c.edge_index = edge_index; c.node_types = node_types;
+  c.N = N; c.E = E; c.edge_logits = edge_logits; c.node_logits = node_logits; c.class_logits = class_logits;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  c.order.kind = EdgeOrder::KNN; c.order.knn = &ka;
+  return mpn_forward(c);
 }
 
 extern "C" int pemp_mpn_prepare(const pemp_mpn_desc* desc, const int64_t* edge_index, const int64_t* node_types,
@@ -4825,20 +4807,18 @@ extern "C" int pemp_mpn_edge_image(const pemp_mpn_desc* desc, const pemp_mpn_wei
     float* eimg = image + embed_image_offset(*desc, *w);
     const bool fixed = embed_fixed_shape(lo);
     const bool comp = embed_composed(lo, prec, *w);
-#define PEMP_EMBED_IMAGE(P, FX)                                                                                  \
-  hipLaunchKernelGGL((embed_image_kernel<P, FX>), dim3(16), dim3(256), 0, as_stream(stream), w->edge_emb, lo,     \
-                     w->emb_bf, w->q0_w, w->q0_b, w->e1_w, w->e1_bf, comp ? w->emb_comp_bf : nullptr,             \
-                     comp ? w->emb_comp_b : nullptr, eimg)
-    if (prec == PEMP_PREC_F16X3) {
-      if (fixed) PEMP_EMBED_IMAGE(2, true);
-      else PEMP_EMBED_IMAGE(2, false);
-    } else if (prec == PEMP_PREC_BF16X3) {
-      if (fixed) PEMP_EMBED_IMAGE(1, true);
-      else PEMP_EMBED_IMAGE(1, false);
-    } else {
-      PEMP_EMBED_IMAGE(0, false);
-    }
-#undef PEMP_EMBED_IMAGE
+    // (five instantiations: the fixed-shape form exists for the split precisions only)
+    with_prec(prec, [&](auto P) {
+      constexpr int PREC = decltype(P)::value;
+      auto launch = [&](auto FX) {
+        hipLaunchKernelGGL((embed_image_kernel<PREC, decltype(FX)::value>), dim3(16), dim3(256), 0, as_stream(stream),
+                           w->edge_emb, lo, w->emb_bf, w->q0_w, w->q0_b, w->e1_w, w->e1_bf,
+                           comp ? w->emb_comp_bf : nullptr, comp ? w->emb_comp_b : nullptr, eimg);
+      };
+      if constexpr (PREC != PEMP_PREC_FP32)
+        if (fixed) return launch(std::true_type{});
+      launch(std::false_type{});
+    });
     PEMP_LAUNCH_CHECK();
   }
   return PEMP_OK;

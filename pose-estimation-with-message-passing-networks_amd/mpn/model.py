@@ -60,6 +60,42 @@ def _rows(logits, n):
     return [logits[r].view(L, 1).squeeze() for r in range(n)]
 
 
+def _preds(edge_logits, node_logits, class_logits, n_rec):
+    """forward's return value: list lengths and .squeeze() semantics of NodeClassificationMPNSimple.py:81-97"""
+    return _rows(edge_logits, n_rec), _rows(node_logits, n_rec + 1), list(class_logits.unbind(0)), [None]
+
+
+class _LogitBuf:
+    """The three logit arrays of a forward in one allocation (one caching-allocator call per forward instead of
+    three): [max(n_rec, 1), E] edge, [n_rec + 1, N] node and [n_rec + 1, N, J] class logits, the node segment at
+    float offset a1 and the class segment at a2, each on a 256-byte boundary. A capacity-mode forward allocates for
+    its capacities and is read back with the batch's counts (views)."""
+
+    def __init__(self, n_rec, N, E, J, device):
+        ne, nn_ = max(n_rec, 1) * E, (n_rec + 1) * N
+        self.n_rec, self.J = n_rec, J
+        self.a1 = (ne + 63) // 64 * 64
+        self.a2 = self.a1 + (nn_ + 63) // 64 * 64
+        self.buf = torch.empty(self.a2 + nn_ * J, dtype=torch.float32, device=device)
+
+    def pending(self, key):
+        """A queued result as _take_cap reads it (from_pending)."""
+        return dict(buf=self.buf, a1=self.a1, a2=self.a2, n_rec=self.n_rec, key=key)
+
+    @classmethod
+    def from_pending(cls, pending, J):
+        self = cls.__new__(cls)
+        self.buf, self.a1, self.a2, self.n_rec, self.J = (pending["buf"], pending["a1"], pending["a2"],
+                                                          pending["n_rec"], J)
+        return self
+
+    def views(self, N, E):
+        """(edge, node, class) logit arrays of a forward over N nodes and E edges."""
+        r, J = self.n_rec, self.J
+        return (self.buf[:max(r, 1) * E].view(max(r, 1), E), self.buf[self.a1:self.a1 + (r + 1) * N].view(r + 1, N),
+                self.buf[self.a2:self.a2 + (r + 1) * N * J].view(r + 1, N, J))
+
+
 def _make_mlp(input_dim, hidden_dims, bn=False, end_with_relu=False):
     """Layer indices as ``layers.py:8-29``: Linear, then (ReLU, [BN]) between Linears."""
     mods = [nn.Linear(input_dim, hidden_dims[0])]
@@ -209,7 +245,7 @@ class NodeClassificationMPNSimple(nn.Module):
         self._folded_key = None
         self._tensors = None
         self._ws = _lib.Workspace()
-        self._desc_key = None
+        self._descs = {}                # counts_in_off -> (key, byref of the descriptor): _descriptor
         # the edge embedding fused into the first edge pass where the library has that form: None (the default) except
         # in a forward the library profiler records, True there too, False never (two launches, the same bits);
         # pemp.h PEMP_MPN_TWO_LAUNCH_FIRST / PEMP_MPN_FUSED_FIRST_PROFILED
@@ -253,6 +289,25 @@ class NodeClassificationMPNSimple(nn.Module):
         f = self.fuse_first_pass
         return 0 if f is None else _lib.MPN_FUSED_FIRST_PROFILED if f else _lib.MPN_TWO_LAUNCH_FIRST
 
+    def _descriptor(self, A, C, t_stride, counts_in_off=False):
+        """byref of the library descriptor for edge_attr width A, node width C and this node_types stride, built when
+        one of those, the precision or fuse_first_pass changes (self._n_rec with it); with counts_in_off the
+        PEMP_MPN_COUNTS_IN_OFFSETS one, cached on its own. (The struct itself is the byref's ``_obj``.)"""
+        dkey = (A, C, self.precision, t_stride, self.fuse_first_pass)
+        ent = self._descs.get(counts_in_off)
+        if ent is None or ent[0] != dkey:
+            steps, aux = self.edge_steps, self.aux_loss_steps
+            self._n_rec = sum(1 for i in range(steps) if i >= steps - aux - 1)
+            flags = self._first_flag() | (_lib.MPN_COUNTS_IN_OFFSETS if counts_in_off else 0)
+            desc = _lib.PempMpnDesc(self.num_types, self.num_joints, steps, aux, self.aggr_code, 64, A, C,
+                                    PRECISIONS[self.precision], t_stride, flags)
+            ent = self._descs[counts_in_off] = (dkey, ctypes.byref(desc))
+        return ent[1]
+
+    # the plain descriptor of the last forward (tests and tools read the edge order back with it)
+    _desc_ref = property(lambda self: self._descs[False][1])
+    _desc = property(lambda self: self._descs[False][1]._obj)
+
     def _forward_blocks(self, x, edge_attr, edge_index, node_types, kwargs):
         """A call over the library's size limit: the nodes are cut into contiguous blocks that no edge crosses
         (each image of a construct_graph batch is such a block; node ids are image-major, ConstructGraph.py:206-231),
@@ -278,10 +333,7 @@ class NodeClassificationMPNSimple(nn.Module):
             for r in range(n_rec + 1):
                 node_logits[r, n0:n1] = pn[r].reshape(-1)
                 class_logits[r, n0:n1] = pc[r]
-        preds_edge = _rows(edge_logits, n_rec)
-        preds_node = _rows(node_logits, n_rec + 1)
-        preds_class = list(class_logits.unbind(0))
-        return preds_edge, preds_node, preds_class, [None]
+        return _preds(edge_logits, node_logits, class_logits, n_rec)
 
     def forward(self, x, edge_attr, edge_index, **kwargs):
         if self.training:    # autograd over the nn layers and the segment kernels of csrc/train.hip (mpn/train.py)
@@ -316,27 +368,12 @@ class NodeClassificationMPNSimple(nn.Module):
             raise ValueError(f"precision={self.precision!r}: expected one of {sorted(PRECISIONS)}")
         fw = self._weights(dev)                               # may fall back to fp32 (weight range)
         A = edge_attr.shape[1] if edge_attr.dim() == 2 else 1
-        dkey = (A, x.shape[1], self.precision, t_stride, self.fuse_first_pass)
-        if self._desc_key != dkey:
-            steps, aux = self.edge_steps, self.aux_loss_steps
-            self._n_rec = sum(1 for i in range(steps) if i >= steps - aux - 1)
-            self._desc = _lib.PempMpnDesc(self.num_types, self.num_joints, steps, aux, self.aggr_code, 64, A,
-                                          x.shape[1], PRECISIONS[self.precision], t_stride, self._first_flag())
-            self._desc_ref = ctypes.byref(self._desc)
-            self._desc_key = dkey
-        desc, n_rec = self._desc_ref, self._n_rec
+        desc = self._descriptor(A, x.shape[1], t_stride)
+        n_rec = self._n_rec
         ws = self._ws.get(L.pemp_mpn_workspace_size(desc, N, E), dev)
         st = _lib.stream(dev)
-        # the three logit arrays share one allocation (one caching-allocator call per forward instead of
-        # three); each segment starts on a 256-byte boundary
-        ne, nn_ = max(n_rec, 1) * E, (n_rec + 1) * N
-        nc = nn_ * self.num_joints
-        a1 = (ne + 63) // 64 * 64
-        a2 = a1 + (nn_ + 63) // 64 * 64
-        buf = torch.empty(a2 + nc, dtype=torch.float32, device=dev)
-        edge_logits = buf[:ne].view(max(n_rec, 1), E)
-        node_logits = buf[a1:a1 + nn_].view(n_rec + 1, N)
-        class_logits = buf[a2:a2 + nc].view(n_rec + 1, N, self.num_joints)
+        lg = _LogitBuf(n_rec, N, E, self.num_joints, dev)
+        edge_logits, node_logits, class_logits = lg.views(N, E)
         if fully is not None:       # the graph constructor's fully graph: closed-form edge order
             noff, offs, B = fully
             _lib.check(L.pemp_mpn_forward_fully(desc, fw.struct_ref, x.data_ptr(), edge_attr.data_ptr(),
@@ -363,12 +400,7 @@ class NodeClassificationMPNSimple(nn.Module):
                                           st))
         if kwargs.get("validate", _VALIDATE or (_DEBUG_SYNC and (sym or fully is not None or knn is not None))):
             _lib.check(L.pemp_mpn_status(desc, N, E, _lib.ptr(ws), _lib.stream(dev)))
-        # list lengths and .squeeze() semantics of NodeClassificationMPNSimple.py:81-97
-        preds_edge = _rows(edge_logits, n_rec)
-        preds_node = _rows(node_logits, n_rec + 1)
-        preds_class = list(class_logits.unbind(0))
-        return preds_edge, preds_node, preds_class, [None]
-
+        return _preds(edge_logits, node_logits, class_logits, n_rec)
 
     def _order_workspace(self, N, E):
         """(descriptor, workspace) of the last forward over N nodes and E edges on the current stream: tests read the
@@ -378,20 +410,15 @@ class NodeClassificationMPNSimple(nn.Module):
 
 
     # ---- capacity mode (graph_constructor.bind_mpn): the forward queued before the detection counts are known ----
-    def _forward_cap(self, x, edge_attr, joint_det, n_cap, e_cap, n_det, det_cap, node_off, B, counts_in_off=False):
-        """Queue pemp_mpn_forward_fully_cap on the capacity buffers of pemp_fully_graph_build_cap (x [n_cap, C],
-        edge_attr [e_cap, A], joint_det [n_cap, 3], node_off [B + 1]) with the detection's device counts n_det.
-        Returns the pending result (logit buffer + the key it was computed under) or None when this model / batch
-        takes the exact forward (training, type summaries, unfused node MLPs, a detection capacity past the
-        closed-form limit, over-size capacities)."""
-        launch = self._prepare_cap(x, edge_attr, joint_det, n_cap, e_cap, n_det, det_cap, node_off, B, counts_in_off)
-        return None if launch is None else launch()
-
     def _prepare_cap(self, x, edge_attr, joint_det, n_cap, e_cap, n_det, det_cap, node_off, B, counts_in_off=False):
-        """_forward_cap in two halves: the host preparation (weights, descriptor, workspace, logit buffer) now,
-        and the returned launch() that queues the call and returns the pending result (or None); None when this
-        model / batch takes the exact forward. The graph constructor prepares before its first launch and calls
-        launch() right after the graph build's, so nothing but the call itself separates the two on the GPU."""
+        """Queue pemp_mpn_forward_fully_cap on the capacity buffers of pemp_fully_graph_build_cap (x [n_cap, C],
+        edge_attr [e_cap, A], joint_det [n_cap, 3], node_off [B + 1]) with the detection's device counts n_det, in
+        two halves: the host preparation (weights, descriptor, workspace, logit buffer) now, and the returned
+        launch() that queues the call and returns the pending result (logit buffer + the key it was computed
+        under), or None when the library refuses. None instead of a launch when this model / batch takes the exact
+        forward (training, type summaries, a detection capacity past the closed-form limit, over-size capacities).
+        The graph constructor prepares before its first launch and calls launch() right after the graph build's,
+        so nothing but the call itself separates the two on the GPU."""
         if self.training or self.node_summary != "not" or _FULLY_OFF or x.device.type != "cuda":
             return None
         if e_cap > self._edge_limit or self.num_types * n_cap > self._node_rows_limit:
@@ -401,34 +428,16 @@ class NodeClassificationMPNSimple(nn.Module):
         node_types = joint_det[:, 2]
         fw = self._weights(dev)
         A = edge_attr.shape[1]
-        dkey = (A, x.shape[1], self.precision, 3, self.fuse_first_pass)
-        if self._desc_key != dkey:
-            steps, aux = self.edge_steps, self.aux_loss_steps
-            self._n_rec = sum(1 for i in range(steps) if i >= steps - aux - 1)
-            self._desc = _lib.PempMpnDesc(self.num_types, self.num_joints, steps, aux, self.aggr_code, 64, A,
-                                          x.shape[1], PRECISIONS[self.precision], 3, self._first_flag())
-            self._desc_ref = ctypes.byref(self._desc)
-            self._desc_key = dkey
-        desc, n_rec = self._desc_ref, self._n_rec
+        desc = self._descriptor(A, x.shape[1], 3)
         if counts_in_off:   # node_off [B + 4]: the build wrote the batch's (N, E, overflow) after the offsets
-            if getattr(self, "_desc_cnt_key", None) != dkey:
-                d = self._desc
-                self._desc_cnt = _lib.PempMpnDesc(d.num_types, d.num_joints, d.steps, d.aux_loss_steps, d.aggr,
-                                                  d.hidden, d.edge_attr_dim, d.node_in_dim, d.precision,
-                                                  d.types_stride, _lib.MPN_COUNTS_IN_OFFSETS | self._first_flag())
-                self._desc_cnt_ref = ctypes.byref(self._desc_cnt)
-                self._desc_cnt_key = dkey
-            desc = self._desc_cnt_ref
+            desc = self._descriptor(A, x.shape[1], 3, True)
         ws = self._ws.get(L.pemp_mpn_workspace_size(desc, n_cap, e_cap), dev)
-        ne, nn_ = max(n_rec, 1) * e_cap, (n_rec + 1) * n_cap
-        a1 = (ne + 63) // 64 * 64
-        a2 = a1 + (nn_ + 63) // 64 * 64
-        buf = torch.empty(a2 + nn_ * self.num_joints, dtype=torch.float32, device=dev)
-        bp = buf.data_ptr()
+        lg = _LogitBuf(self._n_rec, n_cap, e_cap, self.num_joints, dev)
+        bp = lg.buf.data_ptr()
         args = (desc, fw.struct_ref, x.data_ptr(), edge_attr.data_ptr(), node_types.data_ptr(), n_cap, e_cap,
-                n_det.data_ptr(), det_cap, node_off.data_ptr(), B, bp, bp + 4 * a1, bp + 4 * a2, ws.data_ptr(),
+                n_det.data_ptr(), det_cap, node_off.data_ptr(), B, bp, bp + 4 * lg.a1, bp + 4 * lg.a2, ws.data_ptr(),
                 ws.numel(), _lib.stream(dev))
-        result = dict(buf=buf, a1=a1, a2=a2, n_rec=n_rec, key=(dev, self.precision, self._folded_key))
+        result = lg.pending((dev, self.precision, self._folded_key))
 
         def launch():
             rc = L.pemp_mpn_forward_fully_cap(*args)
@@ -447,18 +456,9 @@ class NodeClassificationMPNSimple(nn.Module):
         if e_cap > self._edge_limit or self.num_types * n_cap > self._node_rows_limit:
             return None
         fw = self._weights(dev)
-        dkey = (A, C, self.precision, 3, self.fuse_first_pass)
-        if getattr(self, "_desc_cnt_key", None) != dkey:
-            steps, aux = self.edge_steps, self.aux_loss_steps
-            self._n_rec = sum(1 for i in range(steps) if i >= steps - aux - 1)
-            self._desc_cnt = _lib.PempMpnDesc(self.num_types, self.num_joints, steps, aux, self.aggr_code, 64, A, C,
-                                              PRECISIONS[self.precision], 3,
-                                              _lib.MPN_COUNTS_IN_OFFSETS | self._first_flag())
-            self._desc_cnt_ref = ctypes.byref(self._desc_cnt)
-            self._desc_cnt_key = dkey
-        L = _lib.lib()
-        ws = self._ws.get(L.pemp_mpn_workspace_size(self._desc_cnt_ref, n_cap, e_cap), dev)
-        return self._desc_cnt, fw, ws, (dev, self.precision, self._folded_key)
+        desc = self._descriptor(A, C, 3, True)
+        ws = self._ws.get(_lib.lib().pemp_mpn_workspace_size(desc, n_cap, e_cap), dev)
+        return desc._obj, fw, ws, (dev, self.precision, self._folded_key)
 
     def _attach_cap(self, pending, x, edge_attr, edge_index, joint_det, N, E):
         """Tag construct_graph's output with the queued result (the capacity batch fit: N, E are its counts)."""
@@ -481,14 +481,7 @@ class NodeClassificationMPNSimple(nn.Module):
         if pending["key"] != (x.device, self.precision, self._folded_key):
             return None
         edge_index._pemp_mpn = None                            # one use: a repeated call computes
-        buf, a1, a2, n_rec, J = pending["buf"], pending["a1"], pending["a2"], pending["n_rec"], self.num_joints
-        edge_logits = buf[:max(n_rec, 1) * E].view(max(n_rec, 1), E)
-        node_logits = buf[a1:a1 + (n_rec + 1) * N].view(n_rec + 1, N)
-        class_logits = buf[a2:a2 + (n_rec + 1) * N * J].view(n_rec + 1, N, J)
-        preds_edge = _rows(edge_logits, n_rec)
-        preds_node = _rows(node_logits, n_rec + 1)
-        preds_class = list(class_logits.unbind(0))
-        return preds_edge, preds_node, preds_class, [None]
+        return _preds(*_LogitBuf.from_pending(pending, self.num_joints).views(N, E), pending["n_rec"])
 
 
 def node_blocks(edge_index, N, edge_limit, node_limit):

@@ -1,7 +1,7 @@
 """Model shapes other than the published one: the case table shared by tests/test_mpn_shapes_cpu.py and
 tests/test_gpu_mpn_shapes.py, with the config and graph builders both use.
 
-Every case changes only the listed keys of ``published_mpn_config``; ``mpn_forward_impl`` (csrc/mpn.hip) picks its
+Every case changes only the listed keys of ``published_mpn_config``; ``plan_forward`` (csrc/mpn.hip) picks its
 kernels from exactly these shapes, so each case names the launch site it reaches (``label``: the library
 profiler's label of that site, None where the shape stays on the published kernels)."""
 import functools

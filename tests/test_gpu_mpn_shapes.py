@@ -1,5 +1,5 @@
 """The inference MPN on model shapes other than the published one (tests/mpn_shapes.py): every shape from which
-mpn_forward_impl (csrc/mpn.hip) selects another kernel -- the wide and the generic edge embedding, the generic edge
+plan_forward (csrc/mpn.hip) selects another kernel -- the wide and the generic edge embedding, the generic edge
 head per aggregation and precision, the unfused node / class heads, node embeddings of other input widths and depths
 -- against the CPU oracle at the project's bar (logits within 1e-4), on graphs that cut every tile of those kernels.
 The library profiler's labels show that each fall-back was the kernel that ran."""
