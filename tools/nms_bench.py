@@ -1,6 +1,6 @@
 """Isolated timing of the detection stages at a bench workload's shape: back-to-back pemp_detect calls with only the
 NMS pass (stages = PEMP_DETECT_NMS) and with the whole detection, HIP events on the launch stream.
-usage: python tools/nms_bench.py [workload] [reps] -> one JSON line (PEMP_NMS_QUAD / PEMP_LIB select the variant)"""
+usage: python tools/nms_bench.py [workload] [reps] -> one JSON line (PEMP_LIB selects the library)"""
 import json
 import os
 import sys
@@ -33,7 +33,7 @@ def call(stages):
                              _lib.ptr(det), _lib.ptr(dsc), _lib.ptr(n_det), cap, None, st))
 
 
-out = {"workload": wl_name, "quad": os.environ.get("PEMP_NMS_QUAD", "default"), "bytes": hm.numel() * 4}
+out = {"workload": wl_name, "bytes": hm.numel() * 4}
 # cold: the 256 MB Infinity Cache (MALL) holds most of a 223 MB batch between back-to-back calls; a 1 GiB copy
 # between calls evicts it, as the MPN's traffic does inside a step (events around each call only)
 scrub = torch.empty(2, 512 << 20, dtype=torch.uint8, device=dev)
