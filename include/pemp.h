@@ -642,7 +642,7 @@ int pemp_mpn_status(const pemp_mpn_desc* desc, int64_t N, int64_t E, const void*
  * Labels: detect_nms, detect_top, detect_emit, pack_nodes, fully_graph, edge_features, knn_adj, knn_emit, score_graph,
  * mpn_prepare (the sorting prepare; the closed forms report under mpn_prepare_fully, mpn_prepare_sym and
  * mpn_prepare_knn, so the filter "mpn_prepare" catches all four), node_embed, edge_embed, node_table, edge_step, edge_step_head, node_update, heads, seg_aggr_fwd,
- * seg_aggr_bwd, seg_rows_sum. Model shapes off the published one report their fall-back kernels under labels of
+ * seg_aggr_bwd, seg_rows_sum, edge_mlp_fwd, edge_mlp_bwd, edge_mlp_tree. Model shapes off the published one report their fall-back kernels under labels of
  * their own (the filter is a substring match, so "edge_embed" and "edge_step" still catch them): edge_embed_wide
  * (an embedding layer or edge_attr_dim over 64: weights read from global memory), edge_embed_generic (the LDS
  * embedding for a shape off the fixed A <= 32 -> 32 -> 64 -> 64 -> 64 layout), edge_step_head_generic (a recorded
@@ -733,6 +733,25 @@ int pemp_label_edges(const int64_t* edge_index, int64_t E, const int64_t* node_o
  * Argument errors (unknown kind, T < 1, W, negative sizes, a required NULL pointer, ATTN without scores) are
  * reported before the first HIP call. N == 0 returns 0 at once; E == 0 returns 0 without a launch, out zero-filled
  * (arg -1).
+ *
+ * The fused edge update (csrc/train_edge.hip): mlp_edge(cat([x[dst], x[src], ef])), Linear(2 Wn + We -> 64), ReLU,
+ * Linear(64 -> 64), ReLU, in the per-node-table form. With W1 = [A | B | C] split by columns (A, B: Wn columns
+ * each, C [64][We]) the caller computes P = nf A^T + b1 and Q = nf B^T ([N][64]); then
+ *   h = relu(P[dst] + Q[src] + ef C^T),  e_new = relu(h W2^T + b2)          (exact-fp32 MFMA, k-ordered fmaf chains)
+ * pemp_edge_mlp_fwd: writes h and e_new [E][64]. ef [E][We], We = 64 or 128; src32 / dst32 [E] int32 node ids
+ * (edge_index rows 0 / 1); an id outside [0, N) is never followed and contributes a zero row.
+ * pemp_edge_mlp_bwd: from g = dL/de_new [E][64] and the forward's ef, h, e_new: g2 = g [e_new > 0],
+ * g1 = (g2 W2) [h > 0] (the gradient of the pre-activation of h: dP and dQ are its pemp_seg_rows_sum over
+ * (perm_dst, dst_off) and (perm_src, src_off) at W = 64), g_ef = g1 C [E][We], and the weight gradients
+ * dW2 = g2^T h [64][64], dC = g1^T ef [64][We], db2 = sum_e g2 [64]. The weight gradients are summed without
+ * atomics in an order fixed by E alone (never by the grid or the device): every chunk of 256 consecutive edges is
+ * one fp32 chain in edge order and stores one partial (64 We + 64 64 + 64 floats) into `workspace`
+ * (pemp_edge_mlp_workspace_size(E, We) bytes; 0 for E = 0, non-decreasing in E); the partials are then added in a
+ * pairwise tree, 32 partials per pass (each pass pads its last group of 32 with zeros). No chain over edges is longer than 256 terms.
+ * Every output element is written exactly once; results are bitwise identical from call to call. Argument errors
+ * (We, negative sizes, a required NULL pointer, a workspace that is too small) are reported before the first HIP
+ * call. pemp_edge_mlp_fwd returns 0 at once for N == 0 or E == 0; pemp_edge_mlp_bwd for E == 0 zero-fills the
+ * weight gradients that are not NULL, without a launch. Profiler labels: edge_mlp_fwd, edge_mlp_bwd, edge_mlp_tree.
  * ---------------------------------------------------------------------------------------- */
 int pemp_seg_aggr_fwd(int kind, int T, int64_t N, int64_t E, const float* msgs /*[E][64]*/,
                       const float* scores /*[E] or NULL*/, const int32_t* perm_dst, const int32_t* seg_off,
@@ -745,6 +764,15 @@ int pemp_seg_aggr_bwd(int kind, int T, int64_t N, int64_t E, const float* grad_o
 int pemp_seg_rows_sum(int64_t N, int64_t E, int W, const float* ga /*[E][W]*/, const int32_t* perm_a,
                       const int32_t* off_a /*[N + 1]*/, const float* gb /*[E][W] or NULL*/, const int32_t* perm_b,
                       const int32_t* off_b, float* out /*[N][W]*/, void* stream);
+size_t pemp_edge_mlp_workspace_size(int64_t E, int We);
+int pemp_edge_mlp_fwd(int64_t N, int64_t E, int We, const float* P /*[N][64]*/, const float* Q /*[N][64]*/,
+                      const float* ef /*[E][We]*/, const int32_t* src32, const int32_t* dst32, const float* C /*[64][We]*/,
+                      const float* W2 /*[64][64]*/, const float* b2 /*[64]*/, float* h /*out [E][64]*/,
+                      float* e_new /*out [E][64]*/, void* stream);
+int pemp_edge_mlp_bwd(int64_t N, int64_t E, int We, const float* g /*[E][64]*/, const float* ef, const float* h,
+                      const float* e_new, const float* C, const float* W2, float* g1 /*out [E][64]*/,
+                      float* g_ef /*out [E][We]*/, float* dC /*out [64][We]*/, float* dW2 /*out [64][64]*/,
+                      float* db2 /*out [64]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -152,6 +152,10 @@ SIGNATURES = {
     "pemp_seg_aggr_fwd": (c_i32, [c_i32, c_i32, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pemp_seg_aggr_bwd": (c_i32, [c_i32, c_i32, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pemp_seg_rows_sum": (c_i32, [c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pemp_edge_mlp_workspace_size": (c_sz, [c_i64, c_i32]),
+    "pemp_edge_mlp_fwd": (c_i32, [c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pemp_edge_mlp_bwd": (c_i32, [c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
+                                  c_p]),
 }
 LABEL_OVERFLOW = 1                  # pemp.h PEMP_LABEL_OVERFLOW
 LABEL_CAND_DTYPE = [("g", "<i4"), ("n", "<u4"), ("sim", "<f8")]   # pemp.h pemp_label_cand

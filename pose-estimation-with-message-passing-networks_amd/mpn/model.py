@@ -250,6 +250,10 @@ class NodeClassificationMPNSimple(nn.Module):
         # in a forward the library profiler records, True there too, False never (two launches, the same bits);
         # pemp.h PEMP_MPN_TWO_LAUNCH_FIRST / PEMP_MPN_FUSED_FIRST_PROFILED
         self.fuse_first_pass = None
+        # training mode only (eval never reads it): True runs the edge update mlp_edge(cat([x[dst], x[src], ef])) as
+        # the fused MFMA operator with its own backward (mpn/train.py edge_update); False (the default) keeps the
+        # gather + concatenation + torch GEMM form, whose numerics the training tests pin
+        self.fused_edge_update = False
         self._cap_ok = True   # pemp_step_fully_cap may queue this model's forward (cleared when the library refuses it)
         # one libpemp call addresses r, Q0 and the aggregates with 32-bit byte offsets (pemp_mpn_forward: E, T N
         # < 2^23); larger calls are cut into node blocks no edge crosses (image blocks for construct_graph output)

@@ -10,6 +10,10 @@ operators stock torch would run on float atomics are
 * ``gather_pair``: ``(x[dst], x[src])``, whose backward is one per-node sum over both edge lists;
 * ``permute_rows``: the per-type bucketing of ``TypeAwareNodeUpdate``, a permutation both ways (pure gathers).
 
+With ``model.fused_edge_update = True`` the edge update ``mlp_edge(cat([x[dst], x[src], ef]))`` runs as one fused
+fp32-MFMA operator with a hand-written backward (``edge_update``, ``csrc/train_edge.hip``) next to ``gather_dst``,
+in place of ``gather_pair``, the concatenation and the two torch GEMMs. Off by default.
+
 They consume a ``SegmentPlan`` (sorted edge lists + offsets) built once per graph with torch ops and cached on
 the model. Results are bitwise reproducible from call to call.
 """
@@ -17,6 +21,7 @@ from dataclasses import dataclass
 from typing import Optional
 
 import torch
+import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
@@ -42,6 +47,8 @@ class SegmentPlan:
     bucket_perm: Optional[torch.Tensor] = None    # [E] edge ids sorted by (type[src], edge id)   (T > 1)
     bucket_inv: Optional[torch.Tensor] = None     # [E] its inverse
     bucket_sizes: Optional[list] = None           # 17 host ints: edges per source type
+    src32: Optional[torch.Tensor] = None          # [E] src as int32 (the fused edge update's ids)
+    dst32: Optional[torch.Tensor] = None          # [E] dst as int32
 
 
 def _offsets(keys, n):
@@ -90,6 +97,7 @@ def build_plan(edge_index, node_types, N, T):
     plan.dst_off = plan.seg_off[::T].contiguous()
     plan.perm_src = torch.sort(src, stable=True).indices.to(torch.int32)
     plan.src_off = _offsets(src, N)
+    plan.src32, plan.dst32 = src.to(torch.int32), dst.to(torch.int32)
     return plan
 
 
@@ -198,6 +206,91 @@ class _GatherPair(torch.autograd.Function):
         return out, None
 
 
+class _GatherDst(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, plan):
+        _lib.lib()
+        x = _device_f32("gather_dst x", x)
+        _same_device("gather_dst", plan, x)
+        if x.dim() != 2 or x.shape[0] != plan.N or x.shape[1] not in (64, 128):
+            raise ValueError(f"gather_dst: x {tuple(x.shape)}, expected ({plan.N}, 64 or 128)")
+        ctx.plan, ctx.W = plan, x.shape[1]
+        return x.index_select(0, plan.dst)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        return _rows_sum(ctx.plan, _device_f32("gather_dst grad", grad), ctx.W, by_dst=True), None
+
+
+def _rows_sum(plan, rows, W, by_dst):
+    """[N, W]: the rows [E, W] summed per target (by_dst) or per source node, in list order."""
+    out = torch.empty(plan.N, W, dtype=torch.float32, device=rows.device)
+    perm, off = (plan.perm_dst, plan.dst_off) if by_dst else (plan.perm_src, plan.src_off)
+    _lib.check(_lib.lib().pemp_seg_rows_sum(plan.N, plan.E, W, rows.data_ptr(), perm.data_ptr(), off.data_ptr(), None,
+                                            None, None, out.data_ptr(), _lib.stream(rows.device)))
+    return out
+
+
+_EDGE_WS = _lib.Workspace()      # the weight-gradient partials of pemp_edge_mlp_bwd (per device and stream)
+
+
+class _EdgeMlp(torch.autograd.Function):
+    """e_new = relu(relu(P[dst] + Q[src] + ef C^T) W2^T + b2) (pemp.h pemp_edge_mlp_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, P, Q, ef, C, W2, b2, plan):
+        L = _lib.lib()
+        P, Q, ef = _device_f32("edge_update P", P), _device_f32("edge_update Q", Q), _device_f32("edge_update ef", ef)
+        C, W2, b2 = _device_f32("edge_update C", C), _device_f32("edge_update W2", W2), _device_f32("edge_update b2", b2)
+        _same_device("edge_update", plan, ef)
+        if plan.src32 is None or plan.dst32 is None:
+            raise ValueError("edge_update: the plan carries no src32 / dst32 (build it with build_plan)")
+        We = ef.shape[1] if ef.dim() == 2 else -1
+        if ef.dim() != 2 or ef.shape[0] != plan.E or We not in (64, 128):
+            raise ValueError(f"edge_update: ef {tuple(ef.shape)}, expected ({plan.E}, 64 or 128)")
+        if P.shape != (plan.N, 64) or Q.shape != (plan.N, 64):
+            raise ValueError(f"edge_update: P {tuple(P.shape)}, Q {tuple(Q.shape)}, expected ({plan.N}, 64)")
+        if C.shape != (64, We) or W2.shape != (64, 64) or b2.shape != (64,):
+            raise ValueError(f"edge_update: C {tuple(C.shape)}, W2 {tuple(W2.shape)}, b2 {tuple(b2.shape)}, expected "
+                             f"(64, {We}), (64, 64), (64,)")
+        for name, t in (("P", P), ("Q", Q), ("C", C), ("W2", W2), ("b2", b2)):
+            if t.device != ef.device:
+                raise RuntimeError(f"edge_update: {name} lies on {t.device}, ef on {ef.device}")
+        h = torch.empty(plan.E, 64, dtype=torch.float32, device=ef.device)
+        e_new = torch.empty(plan.E, 64, dtype=torch.float32, device=ef.device)
+        _lib.check(L.pemp_edge_mlp_fwd(plan.N, plan.E, We, P.data_ptr(), Q.data_ptr(), ef.data_ptr(),
+                                       plan.src32.data_ptr(), plan.dst32.data_ptr(), C.data_ptr(), W2.data_ptr(),
+                                       b2.data_ptr(), h.data_ptr(), e_new.data_ptr(), _lib.stream(ef.device)))
+        ctx.plan, ctx.We = plan, We
+        ctx.save_for_backward(ef, h, e_new, C, W2)
+        return e_new
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        L = _lib.lib()
+        plan, We = ctx.plan, ctx.We
+        ef, h, e_new, C, W2 = ctx.saved_tensors
+        g = _device_f32("edge_update grad", grad)
+        dev = g.device
+        g1 = torch.empty(plan.E, 64, dtype=torch.float32, device=dev)
+        g_ef = torch.empty(plan.E, We, dtype=torch.float32, device=dev)
+        dC = torch.empty(64, We, dtype=torch.float32, device=dev)
+        dW2 = torch.empty(64, 64, dtype=torch.float32, device=dev)
+        db2 = torch.empty(64, dtype=torch.float32, device=dev)
+        nbytes = L.pemp_edge_mlp_workspace_size(plan.E, We)
+        ws = _EDGE_WS.get(nbytes, dev)
+        _lib.check(L.pemp_edge_mlp_bwd(plan.N, plan.E, We, g.data_ptr(), ef.data_ptr(), h.data_ptr(), e_new.data_ptr(),
+                                       C.data_ptr(), W2.data_ptr(), g1.data_ptr(), g_ef.data_ptr(), dC.data_ptr(),
+                                       dW2.data_ptr(), db2.data_ptr(), ws.data_ptr(), nbytes, _lib.stream(dev)))
+        need = ctx.needs_input_grad
+        dP = _rows_sum(plan, g1, 64, by_dst=True) if need[0] else None
+        dQ = _rows_sum(plan, g1, 64, by_dst=False) if need[1] else None
+        return dP, dQ, g_ef if need[2] else None, dC if need[3] else None, dW2 if need[4] else None, \
+            db2 if need[5] else None, None
+
+
 class _PermuteRows(torch.autograd.Function):
     """rows[perm] whose backward is grad[inv] (perm a permutation, inv its inverse): a gather both ways."""
 
@@ -222,6 +315,30 @@ def seg_aggregate(msgs, scores, plan, kind):
 def gather_pair(x, plan):
     """(x[dst], x[src]) for node rows x [N, 64 | 128]; the backward sums both gradients per node in one kernel."""
     return _GatherPair.apply(x, plan)
+
+
+def gather_dst(x, plan):
+    """x[dst] for node rows x [N, 64 | 128]; the backward sums the gradient rows per target node."""
+    return _GatherDst.apply(x, plan)
+
+
+def edge_update(nf, ef, plan, mlp_edge):
+    """``mlp_edge(cat([nf[dst], nf[src], ef]))`` [E, 64] without the gathers and the concatenation, for the agnostic
+    ``mlp_edge`` = Linear(2 Wn + We -> 64), ReLU, Linear(64 -> 64), ReLU; nf [N, Wn], ef [E, We], We in (64, 128).
+    The first layer's weight is split by columns, W1 = [A | B | C]: the node tables P = nf A^T + b1 and Q = nf B^T
+    are torch ops (autograd gives the gradients of A, B, b1 and nf), the per-edge rest is one fused kernel each way.
+    fp32 HIP tensors; differentiable in nf, ef and the four parameters."""
+    lin1, lin2 = mlp_edge[0], mlp_edge[2]
+    Wn = nf.shape[1] if nf.dim() == 2 else -1
+    if ef.dim() != 2 or lin1.in_features != 2 * Wn + ef.shape[1] or lin1.out_features != 64 or \
+            (lin2.in_features, lin2.out_features) != (64, 64):
+        raise ValueError(f"edge_update: mlp_edge {lin1.in_features} -> {lin1.out_features} -> {lin2.out_features} "
+                         f"does not fit nf {tuple(nf.shape)}, ef {tuple(ef.shape)}")
+    nf = _device_f32("edge_update nf", nf)
+    W1 = lin1.weight
+    P = F.linear(nf, W1[:, :Wn], lin1.bias)
+    Q = F.linear(nf, W1[:, Wn:2 * Wn])
+    return _EdgeMlp.apply(P, Q, ef, W1[:, 2 * Wn:], lin2.weight, lin2.bias, plan)
 
 
 def permute_rows(rows, perm, inv):
@@ -251,8 +368,12 @@ def _type_aware_messages(mlp_node, xi_e, plan):
 
 
 def _layer(model, layer, plan, nf, ef):
-    x_i, x_j = gather_pair(nf, plan)
-    e_new = layer.mlp_edge(torch.cat([x_i, x_j, ef], dim=1))
+    if getattr(model, "fused_edge_update", False):                    # x[src] is never materialised
+        x_i = gather_dst(nf, plan)
+        e_new = edge_update(nf, ef, plan, layer.mlp_edge)
+    else:
+        x_i, x_j = gather_pair(nf, plan)
+        e_new = layer.mlp_edge(torch.cat([x_i, x_j, ef], dim=1))
     xi_e = torch.cat([x_i, e_new], dim=1)
     if plan.T == 1:                                                   # MPLayer (layers.py:63-86)
         agg = seg_aggregate(layer.mlp_node(xi_e), None, plan, model.aggr_code)

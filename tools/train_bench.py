@@ -4,8 +4,10 @@ usage: python tools/train_bench.py [--iters 30] [--warmup 5] [--out profiles/tra
   * forward + backward of the published attention model (T = 17, STEPS 3) on bench.py's c3 graph (E = 186,048):
     the HIP operators (model.train()) against the same forward with tests/train_oracle's torch operators
     (index_add_ / scatter_reduce, float atomics), same GPU, same process, alternating;
-  * the three operators alone, forward + backward, against their torch forms at that shape, with the bytes each
-    kernel has to move over the time it took, as a share of the achievable HBM rate.
+  * the same step with model.fused_edge_update = True against the unfused one (the default), alternating pairs;
+  * the operators alone, forward + backward, against their torch forms at that shape, with the bytes each
+    kernel has to move over the time it took, as a share of the achievable HBM rate; the fused edge update
+    (tr.edge_update) against the torch concatenation form of the same block.
 torch.cuda.Event timing around each call after a warm-up, medians. The operators' torch forms are the oracle's.
 """
 import argparse
@@ -21,8 +23,17 @@ sys.path.insert(0, ROOT)
 HBM_TBS = 6.3        # achievable HBM rate of the MI355X (float4 copy), TB/s
 
 
+def spread(ts):
+    return statistics.median(ts), min(ts), max(ts)
+
+
 def timed(fn, iters, warmup):
     """Median and spread (min, max) of fn's device time in ms."""
+    return spread(samples(fn, iters, warmup))
+
+
+def samples(fn, iters, warmup):
+    """fn's device time in ms, call by call."""
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
@@ -34,13 +45,14 @@ def timed(fn, iters, warmup):
         b.record()
         b.synchronize()
         ts.append(a.elapsed_time(b))
-    return statistics.median(ts), min(ts), max(ts)
+    return ts
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--pairs", type=int, default=5, help="alternations of the unfused and the fused model step")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_step.md"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -79,6 +91,20 @@ def main():
         res["torch"].append(timed(step_torch, args.iters, args.warmup))
     step = {k: min(v) for k, v in res.items()}
 
+    # the fused edge update against the unfused step (the default, the code above), alternating
+    def step_fused():
+        model.fused_edge_update = True
+        try:
+            step_hip()
+        finally:
+            model.fused_edge_update = False
+
+    pair = {"unfused": [], "fused": []}
+    for _ in range(args.pairs):
+        pair["unfused"] += samples(step_hip, args.iters, args.warmup)
+        pair["fused"] += samples(step_fused, args.iters, args.warmup)
+    fused = {k: spread(v) for k, v in pair.items()}
+
     plan = tr.build_plan(ei, types, N, T)
     src, dst, tsrc = plan.src, plan.dst, plan.type_src
     g = torch.Generator(device=dev).manual_seed(5)
@@ -87,10 +113,10 @@ def main():
     w_out = torch.rand(N * T, 64, generator=g, device=dev) - 0.5
     from pemp_amd import _lib
 
-    def kernel_us(fn):
+    def kernel_us(fn, filt="seg_"):
         """{label: us per launch} of the library's own kernels under fn (its event profiler, one event pair per
         launch: the figure includes the event records' overhead)."""
-        _lib.prof_enable("seg_")
+        _lib.prof_enable(filt)
         for _ in range(args.iters):
             fn()
         torch.cuda.synchronize()
@@ -125,6 +151,41 @@ def main():
                     timed(lambda: run(False), args.iters, args.warmup), nbytes, kernel_us(lambda: run(True)),
                     {"seg_rows_sum": 2 * E * W * 4 + 2 * E * 4 + N * W * 4}))
 
+    # the edge update mlp_edge(cat([x[dst], x[src], ef])) at the model's widths (SKIP: Wn = We = 128)
+    mlp = model.mpn_node_cls.mlp_edge
+    Wn = (mlp[0].in_features) // 3
+    nf0 = torch.rand(N, Wn, generator=g, device=dev) - 0.3
+    ef0 = torch.rand(E, Wn, generator=g, device=dev) - 0.3
+    ge = torch.rand(E, 64, generator=g, device=dev) - 0.5
+
+    def run_edge(form):
+        for p in mlp.parameters():
+            p.grad = None
+        nf, ef = nf0.detach().requires_grad_(True), ef0.detach().requires_grad_(True)
+        if form == "fused":
+            o = tr.edge_update(nf, ef, plan, mlp)
+        elif form == "unfused":                                  # the model's default path
+            o = mlp(torch.cat([*tr.gather_pair(nf, plan), ef], dim=1))
+        else:                                                    # plain torch (index_add_ backward, float atomics)
+            o = mlp(torch.cat([nf[dst], nf[src], ef], dim=1))
+        o.backward(ge)
+    nchunk = (E + 255) // 256
+    part = 4 * (64 * Wn + 64 * 64 + 64)
+    # forward: ef and the ids read, h and e_new written (the P / Q rows come from L2); backward: g, ef, h, e_new read,
+    # g1 and g_ef written, one partial per 256 edges written (and read again by the tree)
+    e_fwd = E * (Wn * 4 + 8 + 512)
+    e_bwd = E * (3 * 256 + Wn * 4 + 256 + Wn * 4) + nchunk * part
+    e_tree = (nchunk + (nchunk + 31) // 32 * 2 + 1) * part
+    e_rows = 2 * (E * (256 + 4) + N * 256)
+    edge_t = {f: timed(lambda f=f: run_edge(f), args.iters, args.warmup) for f in ("fused", "torch", "unfused")}
+    edge_k = kernel_us(lambda: run_edge("fused"), "edge_mlp")
+    edge_k.update({"seg_rows_sum (dP, dQ; each)": v for k, v in kernel_us(lambda: run_edge("fused")).items()})
+    ops.append((f"edge_update We={Wn}", edge_t["fused"], edge_t["torch"], e_fwd + e_bwd + e_tree + e_rows, edge_k,
+                {"edge_mlp_fwd": e_fwd, "edge_mlp_bwd": e_bwd, "edge_mlp_tree": e_tree,
+                 "seg_rows_sum (dP, dQ; each)": e_rows // 2}))
+    ok_model = fused["fused"][0] < fused["unfused"][1]
+    ok_op = edge_t["fused"][0] < edge_t["torch"][0]
+
     lines = ["# Training step of the MPN: HIP graph operators against their torch forms", "",
              f"`python tools/train_bench.py --iters {args.iters} --warmup {args.warmup}` on {torch.cuda.get_device_name(0)}; "
              f"bench.py's c3 graph: N = {N}, E = {E}, T = {T}, STEPS {cfg.STEPS}, attention model. "
@@ -137,6 +198,20 @@ def main():
              f"Ratio torch / HIP: {step['torch'][0] / step['hip'][0]:.2f}. Both forms run the same dense layers "
              "through torch autograd; they differ in the graph operators (and in the per-type message MLPs' "
              "bucketing, a permutation here and boolean masks there).", "",
+             "## The fused edge update (`model.fused_edge_update = True`) against the default", "",
+             f"{args.pairs} alternating pairs of {args.iters} steps (after {args.warmup} warm-up steps each), all "
+             "steps of a form pooled: median (min .. max) in ms.", "",
+             "| form | ms |", "|---|---|",
+             f"| unfused (default; gather_pair, concatenation, torch GEMMs) | {fused['unfused'][0]:.3f} "
+             f"({fused['unfused'][1]:.3f} .. {fused['unfused'][2]:.3f}) |",
+             f"| fused (`tr.gather_dst` + `tr.edge_update`) | {fused['fused'][0]:.3f} "
+             f"({fused['fused'][1]:.3f} .. {fused['fused'][2]:.3f}) |", "",
+             f"Unfused median / fused median: {fused['unfused'][0] / fused['fused'][0]:.3f}. Condition 1 (the fused "
+             f"median below the unfused minimum): {'met' if ok_model else 'NOT met'}. Condition 2 (`edge_update` "
+             f"faster than its torch concatenation form, table below): {'met' if ok_op else 'NOT met'} "
+             f"({edge_t['fused'][0]:.3f} ms against {edge_t['torch'][0]:.3f} ms; the model's own unfused form of the "
+             f"block, `gather_pair` + concatenation + `mlp_edge`: {edge_t['unfused'][0]:.3f} "
+             f"({edge_t['unfused'][1]:.3f} .. {edge_t['unfused'][2]:.3f}) ms).", "",
              "## Operators alone, forward + backward", "",
              "| operator | HIP ms | torch ms | torch / HIP | bytes (MB) | bytes / HIP time (TB/s) | share of 6.3 TB/s |",
              "|---|---|---|---|---|---|---|"]
