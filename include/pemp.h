@@ -462,10 +462,23 @@ typedef struct pemp_mpn_desc {
 /* While the library profiler (pemp_prof_enable) records, a forward keeps the two launches and their labels
  * (edge_embed, edge_step); with this flag it runs the fused pass there too (label edge_first). */
 #define PEMP_MPN_FUSED_FIRST_PROFILED 8
+/* The prelude of a fully-graph forward (edge order, node embedding, wave ranges, first node table) as four launches
+ * of their own. Without it the closed-form order and the fused node embedding share one launch and the ranges and
+ * the first node table a second one (a forward the library profiler records keeps the four and their labels); the
+ * logits are the same bits either way. For A/B runs and tests. */
+#define PEMP_MPN_SEPARATE_PRELUDE 16
 
 size_t pemp_mpn_workspace_size(const pemp_mpn_desc* desc, int64_t N, int64_t E);
 /* LDS bytes of one workgroup of the fused first pass (one workgroup per CU: at most 160 KiB) */
 size_t pemp_mpn_fused_first_lds_bytes(void);
+/* The prelude's grids for N nodes and E edges in B images of at most nmax nodes, T types, edge_grid workgroups per
+ * edge pass and a device of cus compute units (host arithmetic only). out8: blocks per image of the edge order in a
+ * launch of its own, and in the paired launch A (cut down to the CUs the node embedding leaves: a CU holds one block
+ * of launch A at a time); blocks of the node embedding; the block at which the embedding starts in launch A
+ * (out8[1] x B); range-table blocks and all blocks of the wave ranges (0 without edges); blocks of the first node
+ * table; the block at which the table starts in the paired launch B. Launch A has out8[3] + out8[2] blocks,
+ * launch B out8[7] + out8[6]. */
+int pemp_mpn_prelude_grids(int64_t N, int64_t E, int B, int T, int nmax, int edge_grid, int cus, int32_t* out8);
 /* x [N,node_in_dim], edge_attr [E,edge_attr_dim], edge_index [2,E] (row 0 source j, row 1
  * target i), node_types [N] with element stride desc->types_stride (already mapped by
  * sum_node_types; values < T).

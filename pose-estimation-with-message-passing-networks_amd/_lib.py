@@ -14,6 +14,7 @@ ABI_VERSION = 23
 ERR_INVALID_ARG, ERR_HIP, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -3, -4
 BUILD_WRITE_COUNTS = 0x100          # pemp.h PEMP_BUILD_WRITE_COUNTS
 MPN_PREPARED, MPN_COUNTS_IN_OFFSETS, MPN_TWO_LAUNCH_FIRST, MPN_FUSED_FIRST_PROFILED = 1, 2, 4, 8   # pemp.h PEMP_MPN_*
+MPN_SEPARATE_PRELUDE = 16
 
 c_i32, c_i64, c_f32, c_sz, c_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 
@@ -104,6 +105,7 @@ SIGNATURES = {
     "pemp_edge_features": (c_i32, [c_p, c_p, c_i32, c_p, c_p, c_i64, c_i32, c_f32, c_i32, c_p, c_p]),
     "pemp_mpn_workspace_size": (c_sz, [ctypes.POINTER(PempMpnDesc), c_i64, c_i64]),
     "pemp_mpn_fused_first_lds_bytes": (c_sz, []),
+    "pemp_mpn_prelude_grids": (c_i32, [c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
     "pemp_mpn_forward": (c_i32, [ctypes.POINTER(PempMpnDesc), ctypes.POINTER(PempMpnWeights), c_p, c_p, c_p, c_p,
                                  c_i64, c_i64, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "pemp_mpn_forward_fully": (c_i32, [ctypes.POINTER(PempMpnDesc), ctypes.POINTER(PempMpnWeights), c_p, c_p, c_p,

@@ -1729,12 +1729,25 @@ __device__ inline void edge_positions_fill(const int* __restrict__ seg, int* s_d
 
 // The first RB blocks fill the range tables, the others the segment positions (two short chains of dependent loads
 // side by side instead of one after the other).
-__global__ __launch_bounds__(256) void edge_ranges_kernel(const int* seg, const int* wg_start, int* s_dst, int T,
-                                                          int64_t N, int G, int4* ranges, const int64_t* ne, int RB) {
-  if (ne) N = ne[0];   // capacity mode: the device-side node count (N: the capacity)
-  if ((int)blockIdx.x < RB) edge_ranges_fill(seg, wg_start, s_dst, T, N, G, ranges, blockIdx.x, RB);
-  else edge_positions_fill(seg, s_dst, T, N, blockIdx.x - RB, gridDim.x - RB);
+struct EdgeRangesArgs {
+  const int *seg, *wg_start;
+  int* s_dst;
+  int T;
+  int64_t N;
+  int G;
+  int4* ranges;
+  const int64_t* ne;   // capacity mode: the device-side node count (N: the capacity)
+  int RB, blocks;      // range-table blocks, and all blocks of the role
+};
+
+// block bx of a.blocks (the body of edge_ranges_kernel, and a role of prelude_b_kernel)
+__device__ __forceinline__ void edge_ranges_role(const EdgeRangesArgs& a, int bx) {
+  const int64_t N = a.ne ? a.ne[0] : a.N;
+  if (bx < a.RB) edge_ranges_fill(a.seg, a.wg_start, a.s_dst, a.T, N, a.G, a.ranges, bx, a.RB);
+  else edge_positions_fill(a.seg, a.s_dst, a.T, N, bx - a.RB, a.blocks - a.RB);
 }
+
+__global__ __launch_bounds__(256) void edge_ranges_kernel(EdgeRangesArgs a) { edge_ranges_role(a, blockIdx.x); }
 
 // 16-byte LDS-DMA load per lane into the wave-contiguous LDS block at `l` (lane i -> l + 16 i bytes).
 // (A non-template function: hipcc drops the host stub of a kernel template that calls the builtin
@@ -2735,14 +2748,14 @@ static size_t node_rows_lds_bytes(const NodeRowsArgs& a) {
   return (size_t)(3 * 16 * RS + region) * sizeof(float);
 }
 
-__global__ __launch_bounds__(256) void node_rows_kernel(NodeRowsArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+// 16-node tile bx over the workgroup's dynamic LDS (the body of node_rows_kernel, and a role of prelude_a_kernel)
+__device__ __forceinline__ void node_rows_role(const NodeRowsArgs& a, float* lds, int bx) {
   float* xs = lds;
   float* act0 = lds + 16 * RS;
   float* act1 = act0 + 16 * RS;
   float* wreg = act1 + 16 * RS;                  // one embedding layer at a time, then the heads
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
-  const int64_t n0 = (int64_t)blockIdx.x * 16, N = a.ne ? a.ne[0] : a.N;
+  const int64_t n0 = (int64_t)bx * 16, N = a.ne ? a.ne[0] : a.N;
   if (n0 >= N) return;   // (capacity grids)
   const bool heads = a.node_out != nullptr;
   float *node_out = a.node_out, *node_out2 = a.node_out2, *class_out = a.class_out, *class_out2 = a.class_out2;
@@ -2879,6 +2892,11 @@ __global__ __launch_bounds__(256) void node_rows_kernel(NodeRowsArgs a) {
   }
 }
 
+__global__ __launch_bounds__(256) void node_rows_kernel(NodeRowsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  node_rows_role(a, lds, blockIdx.x);
+}
+
 // Node table NT = [x0 | x] · pre_w^T + pre_b for the next edge pass. 1-D grid of
 // (16 TILES-node chunk, 64-column group) workgroups, chunk-major; each of the 4 waves owns one 16-column
 // block (weight fragment in registers, loaded before the barrier) and walks the chunk's TILES node
@@ -2900,10 +2918,6 @@ struct NodeTableArgs {
   const float* upd_b;
 };
 
-// below this many edges (capacity) the prelude stays on the launch stream: at c2 (one image, ~22k edges) the fork
-// and join waits (7 + 11 us) cost more than the overlap buys: step span 141 vs 165 us, images/s +18 %
-// (profiles/r06_c2_serial_prelude.md)
-constexpr int64_t SIDE_MIN_E = 65536;
 // the middle steps' node update runs inside the node-table launch while its aggregate re-reads (N T 256 B x column
 // groups) stay below this many MB
 constexpr int64_t NODE_SUM_TABLE_MAX_MB = 16;
@@ -2914,12 +2928,12 @@ constexpr int TBL_TILES = 2;           // 16-node tiles per workgroup
 // SUM: the node update x = ReLU(b + sum_t agg[n, t]) (node_rows_kernel ROWS_SUM, same operations and order) is
 // computed here for the tile's 16 rows, by every column group of the tile (the aggregates are re-read from L2 by
 // each group instead of a separate launch writing x and this one reading it back); group 0 also stores x.
-template <int PREC, int TILES = TBL_TILES, bool SUM = false>
-__global__ __launch_bounds__(256) void node_table_kernel(NodeTableArgs a) {
+// block bx over xs [16 TILES][RS] of LDS (the body of node_table_kernel, and a role of prelude_b_kernel)
+template <int PREC, int TILES, bool SUM>
+__device__ __forceinline__ void node_table_role(const NodeTableArgs& a, float* xs, int bx) {
   static_assert(!SUM || TILES == 1, "the summing variant takes one 16-node tile per workgroup");
-  __shared__ __attribute__((aligned(16))) float xs[16 * TILES * RS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
-  const int chunk = blockIdx.x / a.groups, grp = blockIdx.x - chunk * a.groups;
+  const int chunk = bx / a.groups, grp = bx - chunk * a.groups;
   const int64_t n0 = (int64_t)chunk * 16 * TILES, N = a.ne ? a.ne[0] : a.N;
   if (n0 >= N) return;   // (capacity grids)
   const int nob = a.NO / 16, ob = grp * 4 + wave, obc = min(ob, nob - 1);
@@ -3054,6 +3068,25 @@ __global__ __launch_bounds__(256) void node_table_kernel(NodeTableArgs a) {
     }
     if (nn < N) st4(a.NT + nn * a.NO + 16 * ob + 4 * g, acc[0], acc[1], acc[2], acc[3]);
   }
+}
+
+template <int PREC, int TILES = TBL_TILES, bool SUM = false>
+__global__ __launch_bounds__(256) void node_table_kernel(NodeTableArgs a) {
+  __shared__ __attribute__((aligned(16))) float xs[16 * TILES * RS];
+  node_table_role<PREC, TILES, SUM>(a, xs, blockIdx.x);
+}
+
+// Launch B of the paired prelude (Forward::prelude): the wave ranges and segment positions of the edge order
+// (blocks [0, split), edge_ranges_role) beside the first node table (blocks [split, gridDim.x), node_table_role).
+// Both read what launch A and the launches before it wrote and nothing of each other; no workgroup waits for
+// another. The range blocks come first: each is one chain of dependent loads as long as the whole role, the table's
+// are many and short.
+template <int PREC>
+__global__ __launch_bounds__(256) void prelude_b_kernel(EdgeRangesArgs ra, NodeTableArgs ta, int split) {
+  __shared__ __attribute__((aligned(16))) float xs[16 * TBL_TILES * RS];
+  const int bx = blockIdx.x;   // (block-uniform dispatch)
+  if (bx < split) edge_ranges_role(ra, bx);
+  else node_table_role<PREC, TBL_TILES, false>(ta, xs, bx - split);
 }
 
 static int grid1d(int64_t total, int block, int cap = 65536) {
@@ -3231,16 +3264,32 @@ struct FullyPrepArgs {
   const int64_t* ne;   // capacity mode: device-side (N, E, overflow); an overflowed batch prepares as empty images
 };
 
-__global__ __launch_bounds__(256) void fully_prepare_kernel(FullyPrepArgs a) {
-  __shared__ int cnt_bt[FULLY_MAXB][MAXT];
-  __shared__ long long et_sh[MAXT], cb_sh[MAXT];
-  __shared__ int tbase[MAXT + 1];        // sum_{t' < t} E_t' (fits int: E < 2^31)
-  __shared__ int noff[FULLY_MAXB + 1];
-  __shared__ int sorted[FULLY_MAXN], lty[FULLY_MAXN];
-  __shared__ int tstart_l[MAXT + 1], gt_sh[MAXT];
-  __shared__ int bad_sh;
-  __shared__ long long eoff_sh;
-  const int b = blockIdx.y, T = a.T, B = a.B;
+// the LDS of one fully_prepare workgroup
+struct FullyPrepLds {
+  long long et_sh[MAXT], cb_sh[MAXT];
+  long long eoff_sh;
+  int cnt_bt[FULLY_MAXB][MAXT];
+  int tbase[MAXT + 1];        // sum_{t' < t} E_t' (fits int: E < 2^31)
+  int noff[FULLY_MAXB + 1];
+  int sorted[FULLY_MAXN], lty[FULLY_MAXN];
+  int tstart_l[MAXT + 1], gt_sh[MAXT];
+  int bad_sh;
+};
+
+// block (bx of gx, image by) over its LDS (the body of fully_prepare_kernel, and a role of prelude_a_kernel)
+__device__ __forceinline__ void fully_prepare_role(const FullyPrepArgs& a, FullyPrepLds& s, int bx, int by, int gx) {
+  auto& cnt_bt = s.cnt_bt;
+  auto& et_sh = s.et_sh;
+  auto& cb_sh = s.cb_sh;
+  auto& tbase = s.tbase;
+  auto& noff = s.noff;
+  auto& sorted = s.sorted;
+  auto& lty = s.lty;
+  auto& tstart_l = s.tstart_l;
+  auto& gt_sh = s.gt_sh;
+  int& bad_sh = s.bad_sh;
+  long long& eoff_sh = s.eoff_sh;
+  const int b = by, T = a.T, B = a.B;
   const int64_t N = a.ne ? a.ne[0] : a.N;
   const bool empty = a.ne && a.ne[2];   // capacity overflow: node_off was not written
   for (int i = threadIdx.x; i <= B; i += 256) noff[i] = empty ? 0 : (int)a.node_off[i];
@@ -3314,7 +3363,7 @@ __global__ __launch_bounds__(256) void fully_prepare_kernel(FullyPrepArgs a) {
   const long long eoff = eoff_sh;
   // FULLY_PARTS consecutive threads per segment, entry m of the segment on thread (m - s0) % FULLY_PARTS: its slot is
   // the segment start + its rank, one less past d when d itself is of type t (d is left out)
-  for (int q = blockIdx.x * 256 + threadIdx.x; q < T * nb * FULLY_PARTS; q += gridDim.x * 256) {
+  for (int q = bx * 256 + threadIdx.x; q < T * nb * FULLY_PARTS; q += gx * 256) {
     const int sq = q / FULLY_PARTS, part = q - sq * FULLY_PARTS;
     const int t = sq / nb, dl = sq - t * nb;
     const int s0 = tstart_l[t], s1 = tstart_l[t + 1];
@@ -3337,7 +3386,7 @@ __global__ __launch_bounds__(256) void fully_prepare_kernel(FullyPrepArgs a) {
       a.s_orig[p] = (int)(eoff + (long long)i * (nb - 1) + (dl < i ? dl : dl - 1));
     }
   }
-  if (blockIdx.x == 0 && blockIdx.y == 0) {
+  if (bx == 0 && by == 0) {
     if (threadIdx.x == 0) {
       a.seg[(int64_t)T * N] = tbase[T];
       a.err[0] = bad_sh ? 2 : 0;
@@ -3345,6 +3394,27 @@ __global__ __launch_bounds__(256) void fully_prepare_kernel(FullyPrepArgs a) {
     }
     type_split(tbase, tbase[T], T, a.Gsplit, gt_sh, a.wg_start);
   }
+}
+
+__global__ __launch_bounds__(256) void fully_prepare_kernel(FullyPrepArgs a) {
+  __shared__ FullyPrepLds s;
+  fully_prepare_role(a, s, blockIdx.x, blockIdx.y, gridDim.x);
+}
+
+// Launch A of the paired prelude (Forward::prelude): the closed-form edge order (blocks [0, split): block x of gx
+// of image y at y gx + x, fully_prepare_role) beside the node embedding (blocks [split, gridDim.x): one 16-node tile
+// each, node_rows_role in ROWS_EMBED mode). Both read the call's inputs and what earlier launches wrote, nothing of
+// each other; no workgroup waits for another. The order's blocks come first: its chain (order -> ranges) feeds the
+// larger consumer and its blocks are the longer ones. Dynamic LDS: the larger of the two roles' (prelude_a_lds_bytes).
+__global__ __launch_bounds__(256) void prelude_a_kernel(FullyPrepArgs fa, NodeRowsArgs na, int split, int gx) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int bx = blockIdx.x;   // (block-uniform dispatch)
+  if (bx < split) fully_prepare_role(fa, *reinterpret_cast<FullyPrepLds*>(lds), bx % gx, bx / gx, gx);
+  else node_rows_role(na, lds, bx - split);
+}
+
+static size_t prelude_a_lds_bytes(const NodeRowsArgs& na) {
+  return std::max(node_rows_lds_bytes(na), sizeof(FullyPrepLds));
 }
 
 // ---- Symmetric prepare: edge_index sorted by (src, dst) without duplicates and symmetric (PyG to_undirected's
@@ -3915,48 +3985,6 @@ extern "C" int pemp_diag_stamps(void* buf, int pass) {
 }
 #endif
 
-// ---- side stream of a launch stream (the concurrent prelude of a forward, Forward::prelude) ----------------
-struct SideStream {
-  hipStream_t s = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-  std::mutex mu;   // held from the fork to the join enqueue: calls sharing a launch stream pair up
-};
-
-static bool serial_prelude() {
-  static const bool v = getenv("PEMP_SERIAL_PRELUDE") != nullptr;
-  return v;
-}
-
-// one per (device, launch stream), created on first use and kept; nullptr if HIP refuses (serial then)
-static SideStream* side_stream_for(hipStream_t st) {
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, SideStream*> table;
-  int cur = 0;
-  if (hipGetDevice(&cur) != hipSuccess) return nullptr;
-  int dev = cur;
-  if (st) {
-    hipDevice_t d;
-    if (hipStreamGetDevice(st, &d) == hipSuccess) dev = (int)d;
-  }
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = table.find({dev, st});
-  if (it != table.end()) return it->second;
-  if (dev != cur && hipSetDevice(dev) != hipSuccess) return nullptr;
-  SideStream* ss = new SideStream();
-  // (default priority: at the device's highest the stream gained nothing at c3 / c5 and lost 12 % at c3knn10,
-  // DESIGN.md section 4)
-  const bool ok = hipStreamCreateWithFlags(&ss->s, hipStreamNonBlocking) == hipSuccess &&
-                  hipEventCreateWithFlags(&ss->fork, hipEventDisableTiming) == hipSuccess &&
-                  hipEventCreateWithFlags(&ss->join, hipEventDisableTiming) == hipSuccess;
-  if (dev != cur) (void)hipSetDevice(cur);
-  if (!ok) {
-    (void)hipGetLastError();
-    return nullptr;   // (the partial objects are leaked once; the forward runs serially)
-  }
-  table[{dev, st}] = ss;
-  return ss;
-}
-
 // ---- the inference forward: what a call is given (ForwardCall), its argument checks, everything derived from it
 // on the host (ForwardPlan), and the launches (Forward) ------------------------------------------------------------
 // where the type-major edge order of a forward comes from
@@ -4064,6 +4092,45 @@ static int check_forward_args(const ForwardCall& c) {
 // in a launch of its own ahead of it)
 constexpr int NODE_UPDATE_MLP = -1;
 
+// The grids of the prelude's four kernels (order, node embedding, wave ranges, first node table) and, for the paired
+// form (Forward::prelude), the block at which the second role starts in each of its two launches. Eight ints in this
+// order: pemp_mpn_prelude_grids.
+struct PreludeGrids {
+  int prep_gx;                    // fully_prepare in a launch of its own: blocks per image (x B images)
+  int a_gx;                       // ... and in launch A (see below)
+  int rows_blocks;                // node embedding: 16-node tiles
+  int a_split;                    // launch A: [0, a_split = a_gx B) the order, then rows_blocks of the embedding
+  int ranges_rb, ranges_blocks;   // edge_ranges: range-table blocks, and all blocks (none without edges)
+  int table_blocks;               // node table: 16 TBL_TILES-node chunks x column groups
+  int b_split;                    // launch B: [0, b_split) the ranges, [b_split, b_split + table_blocks) the table
+};
+
+// B images of at most nmax nodes (0: no closed-form order), G workgroups per edge pass, a device of `cus` CUs.
+// Every block of launch A asks for the node embedding's LDS (the whole embedding image, ~121 KB at the published
+// shape), so a CU holds one of them at a time, where it holds several blocks of the order's own launch. The order's
+// share is therefore cut down to the CUs the embedding leaves (its segment loop strides by the grid: the same
+// arrays from any grid, and every block repeats the per-batch counts, so fewer blocks do less in all). Where the
+// embedding's tiles alone fill the device (N > 16 cus) the order keeps one block per image and the launch's blocks
+// run in rounds, in block order: the order's first, then the embedding's as CUs come free -- slower than the two
+// launches side by side would be, still correct: no block waits for another.
+static PreludeGrids prelude_grids(int64_t N, int64_t E, int B, int T, int nmax, int G, int cus) {
+  PreludeGrids g{};
+  // FULLY_PARTS threads per (type, target) segment (a per-edge mapping with binary searches measured 41 us
+  // vs 15 us at C3)
+  g.prep_gx = (int)std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)T * nmax * FULLY_PARTS + 511) / 512));
+  g.rows_blocks = (int)((N + 15) / 16);
+  g.a_gx = B > 0 ? std::max(1, std::min(g.prep_gx, (cus - g.rows_blocks) / B)) : g.prep_gx;
+  g.a_split = g.a_gx * B;
+  if (E > 0) {
+    g.ranges_rb = std::min(64, (G * (EDGE_WAVES + 12) + 255) / 256);
+    g.ranges_blocks = g.ranges_rb + (int)std::min<int64_t>(1024, (E + 255) / 256);
+  }
+  const int groups = ((128 + 64 * T) / 16 + 3) / 4;
+  g.table_blocks = (int)(((N + 16 * TBL_TILES - 1) / (16 * TBL_TILES)) * groups);
+  g.b_split = g.ranges_blocks;
+  return g;
+}
+
 // Everything a forward derives from its call on the host, each value once. Nothing here launches.
 struct ForwardPlan {
   int T, J, steps, aux;
@@ -4084,7 +4151,8 @@ struct ForwardPlan {
   int node_mode;
   bool sum_in_table;    // middle steps: the node update inside the node-table launch (node_step)
   bool fused_first;
-  bool side;            // the first node step on the side stream (Forward::prelude)
+  PreludeGrids grids;
+  bool paired;          // the prelude as two launches of two roles each (Forward::prelude)
 };
 
 static ForwardPlan plan_forward(const ForwardCall& c) {
@@ -4114,8 +4182,10 @@ static ForwardPlan plan_forward(const ForwardCall& c) {
   p.NO = 128 + 64 * p.T;
   p.table_prec = d.precision != PEMP_PREC_FP32 && w.pre_bf ? d.precision : PEMP_PREC_FP32;
   p.table_groups = (p.NO / 16 + 3) / 4;
-  p.node_grid = (unsigned)((N + 15) / 16);
-  p.table_grid = (unsigned)(((N + 16 * TBL_TILES - 1) / (16 * TBL_TILES)) * p.table_groups);
+  p.grids = prelude_grids(N, E, c.order.kind == EdgeOrder::FULLY ? c.order.B : 0, p.T, c.order.nmax, p.edge_grid,
+                          num_cus());
+  p.node_grid = (unsigned)p.grids.rows_blocks;
+  p.table_grid = (unsigned)p.grids.table_blocks;
   p.table_grid1 = (unsigned)(((N + 15) / 16) * p.table_groups);
   p.node_mode = p.upd_fused ? ROWS_SUM : (w.upd_w || w.upd_mlp.n_layers > 0) ? NODE_UPDATE_MLP : ROWS_COPY;
   // (every column group re-reads the tile's aggregates: worth it while those re-reads stay small -- C2 -- not at
@@ -4134,37 +4204,14 @@ static ForwardPlan plan_forward(const ForwardCall& c) {
                   p.emb_lds && p.comp && w.edge_img &&
                   prof_repeat("edge_step") == 1 &&
                   (!prof_active() || (d.flags & PEMP_MPN_FUSED_FIRST_PROFILED));
-  // Serial below SIDE_MIN_E edges, when the library profiler is on (per-kernel event timing on the launch stream) or
-  // with PEMP_SERIAL_PRELUDE set.
-  p.side = E >= SIDE_MIN_E && p.steps >= 1 && !prof_active() && !serial_prelude();
+  // The paired prelude: the closed-form order beside the node embedding, then the wave ranges beside the first node
+  // table. The separate launches stay for the other prepares (several launches each), embedding widths that take
+  // rows_mlp, a forward without iterations, one the library profiler records (its labels are those of the separate
+  // kernels) and PEMP_MPN_SEPARATE_PRELUDE.
+  p.paired = c.order.kind == EdgeOrder::FULLY && !(d.flags & (PEMP_MPN_PREPARED | PEMP_MPN_SEPARATE_PRELUDE)) &&
+             p.fused_embed && p.steps >= 1 && !prof_active();
   return p;
 }
-
-// A forward's use of its launch stream's side stream: forked from the launch stream here, joined back into it (and
-// the pairing mutex released) by join() or on leaving the scope, whichever comes first -- on every exit path.
-struct SideFork {
-  SideStream* ss_;
-  const hipStream_t st_;
-  std::unique_lock<std::mutex> lock_;
-  SideFork(SideStream* ss, hipStream_t st) : ss_(ss), st_(st) {
-    if (!ss_) return;
-    lock_ = std::unique_lock<std::mutex>(ss_->mu);
-    if (hipEventRecord(ss_->fork, st_) != hipSuccess || hipStreamWaitEvent(ss_->s, ss_->fork, 0) != hipSuccess) {
-      lock_.unlock();
-      ss_ = nullptr;   // (serial then)
-    }
-  }
-  ~SideFork() { join(); }
-  hipStream_t stream() const { return ss_ ? ss_->s : st_; }
-  void join() {
-    if (!ss_) return;
-    // (a failed join is reported by the next launch check: both calls only enqueue)
-    (void)hipEventRecord(ss_->join, ss_->s);
-    (void)hipStreamWaitEvent(st_, ss_->join, 0);
-    lock_.unlock();
-    ss_ = nullptr;
-  }
-};
 
 // The launches of one forward. Every member function enqueues and returns a PEMP_* code.
 struct Forward {
@@ -4172,7 +4219,6 @@ struct Forward {
   const ForwardPlan& p;
   const MpnWs ws;
   const hipStream_t st;       // the launch stream
-  hipStream_t nst;            // stream of the node kernels (the first node step may run on the side stream)
   const int64_t* ne = nullptr;      // capacity mode: the device-side {N, E}
   const float* node_img = nullptr;  // LDS image of the node-side MLPs
   const float* eimg = nullptr;      // the edge-pass weight image
@@ -4182,7 +4228,7 @@ struct Forward {
 
   Forward(const ForwardCall& call, const ForwardPlan& plan)
       : c(call), p(plan), ws(mpn_carve(call.workspace, plan.T, call.N, call.E, nullptr)), st(as_stream(call.stream)),
-        nst(st), r_cur(ws.EA), r_next(ws.EB) {}
+        r_cur(ws.EA), r_next(ws.EB) {}
 
   bool recorded(int it) const { return it >= p.steps - p.aux - 1; }
   bool last(int it) const { return it + 1 == p.steps; }
@@ -4222,14 +4268,10 @@ struct Forward {
     if (c.desc->flags & PEMP_MPN_PREPARED) return PEMP_OK;
     switch (c.order.kind) {
       case EdgeOrder::FULLY: {
-        FullyPrepArgs fa{c.order.node_off, c.order.B, c.node_types, p.tstride, c.N, p.T, p.edge_grid,
-                         ws.seg, ws.wg_start, ws.s_src, ws.s_dst, ws.s_orig, ws.err, ne};
-        // FULLY_PARTS threads per (type, target) segment (a per-edge mapping with binary searches measured 41 us
-        // vs 15 us at C3)
-        const unsigned gx = (unsigned)std::max<int64_t>(
-            1, std::min<int64_t>(64, ((int64_t)p.T * c.order.nmax * FULLY_PARTS + 511) / 512));
+        const FullyPrepArgs fa = fully_args();
         ProfScope prof("mpn_prepare_fully", st);
-        hipLaunchKernelGGL(fully_prepare_kernel, dim3(gx, (unsigned)c.order.B), dim3(256), 0, st, fa);
+        hipLaunchKernelGGL(fully_prepare_kernel, dim3((unsigned)p.grids.prep_gx, (unsigned)c.order.B), dim3(256), 0, st,
+                           fa);
         PEMP_LAUNCH_CHECK();
         return PEMP_OK;
       }
@@ -4249,17 +4291,25 @@ struct Forward {
     }
   }
 
+  FullyPrepArgs fully_args() const {
+    return FullyPrepArgs{c.order.node_off, c.order.B, c.node_types, p.tstride, c.N, p.T, p.edge_grid,
+                         ws.seg, ws.wg_start, ws.s_src, ws.s_dst, ws.s_orig, ws.err, ne};
+  }
+
   // the passes' per-wave range table (static across iterations), right behind the order: its chains of dependent
   // small loads stay off the edge embedding's workgroups
   int launch_ranges() {
     if (c.E == 0 || p.steps < 1) return PEMP_OK;
-    // (behind the range table's blocks: the per-edge segment positions, one edge per thread)
-    const int rg_blocks = std::min(64, (p.edge_grid * (EDGE_WAVES + 12) + 255) / 256);
-    const int pos_blocks = (int)std::min<int64_t>(1024, (c.E + 255) / 256);
-    hipLaunchKernelGGL(edge_ranges_kernel, dim3((unsigned)(rg_blocks + pos_blocks)), dim3(256), 0, st, ws.seg,
-                       ws.wg_start, ws.s_dst, p.T, c.N, p.edge_grid, ws.ranges, ne, rg_blocks);
+    const EdgeRangesArgs ra = ranges_args();
+    hipLaunchKernelGGL(edge_ranges_kernel, dim3((unsigned)ra.blocks), dim3(256), 0, st, ra);
     PEMP_LAUNCH_CHECK();
     return PEMP_OK;
+  }
+
+  // (behind the range table's blocks: the per-edge segment positions, one edge per thread)
+  EdgeRangesArgs ranges_args() const {
+    return EdgeRangesArgs{ws.seg, ws.wg_start, ws.s_dst, p.T, c.N, p.edge_grid, ws.ranges, ne, p.grids.ranges_rb,
+                          p.grids.ranges_blocks};
   }
 
   // ---- edge embedding: its own launch writes Q0 and R0 = Q0 + W1_e_cur · e_init (edge_embed_kernel;
@@ -4301,40 +4351,15 @@ struct Forward {
     return PEMP_OK;
   }
 
-  // x for the next stage (mode) + heads when slot >= 0, then the node table when `table`
-  int node_step(int mode, bool table, int slot, bool dup) {
+  // node_rows_kernel's arguments: x by `mode`, heads into slot (and slot + 1 when dup) when slot >= 0
+  NodeRowsArgs rows_args(int mode, int slot, bool dup) const {
     const pemp_mpn_weights& w = *c.w;
     const int64_t N = c.N;
-    const int T = p.T, J = p.J;
-    // middle steps of the attention model (update block in the edge pass, no heads): the node update runs inside the
-    // node-table launch (node_table_kernel<PREC, 1, true>) instead of a launch of its own
-    if (mode == ROWS_SUM && table && slot < 0 && p.sum_in_table) {
-      NodeTableArgs ta{ws.X, N, w.pre_w, w.pre_b, w.pre_bf, p.NO, p.table_groups, ws.NT, ne, ws.agg, ws.seg, T,
-                       w.upd_b};
-      ProfScope prof("node_update_table", nst);
-      with_prec(p.table_prec, [&](auto P) {
-        hipLaunchKernelGGL((node_table_kernel<decltype(P)::value, 1, true>), dim3(p.table_grid1), dim3(256), 0, nst, ta);
-      });
-      PEMP_LAUNCH_CHECK();
-      return PEMP_OK;
-    }
-    if (mode == NODE_UPDATE_MLP && w.upd_mlp.n_layers > 0) {   // hierarchical update MLP (dense-folded)
-      NodeMlpArgs ma{ws.agg, ws.seg, T, N, w.upd_mlp, nmlp_max_out(w.upd_mlp), ws.X, ne};
-      ProfScope prof("node_update", nst);
-      hipLaunchKernelGGL(node_mlp_kernel, dim3(p.node_grid), dim3(256), nmlp_lds_bytes(T, w.upd_mlp), nst, ma);
-      PEMP_LAUNCH_CHECK();
-      mode = ROWS_NONE;
-    } else if (mode == NODE_UPDATE_MLP) {                      // update MLP on non-linear aggregates
-      NodeUpdateArgs ua{ws.agg, ws.seg, T, N, w.upd_w, w.upd_b, ws.X, ne};
-      ProfScope prof("node_update", nst);
-      hipLaunchKernelGGL(node_update_kernel, dim3(p.node_grid, 4), dim3(64 * UPD_WAVES), 0, nst, ua);
-      PEMP_LAUNCH_CHECK();
-      mode = ROWS_NONE;
-    }
+    const int J = p.J;
     NodeRowsArgs na{};
     na.mode = mode;
     if (mode == ROWS_EMBED) { na.x_in = c.x; na.in_ld = c.desc->node_in_dim; }
-    na.agg = ws.agg; na.seg = ws.seg; na.T = T; na.upd_b = w.upd_b; na.N = N; na.X = ws.X;
+    na.agg = ws.agg; na.seg = ws.seg; na.T = p.T; na.upd_b = w.upd_b; na.N = N; na.X = ws.X;
     na.node_head = w.node_head; na.class_head = w.class_head; na.J = J;
     na.ne = ne;
     if (slot >= 0 && p.fused_heads && ne) {   // capacity mode: bases, the kernel places rows slot (+ 1) of its N
@@ -4353,37 +4378,101 @@ struct Forward {
     na.head_off = p.fused_embed ? mlp_lds_floats(w.node_emb) : 0;
     na.head_floats = mlp_lds_floats(w.node_head) + mlp_lds_floats(w.class_head);
     na.emb_whole = mode == ROWS_EMBED && node_emb_whole(w.node_emb);
+    return na;
+  }
+
+  NodeTableArgs table_args() const {
+    return NodeTableArgs{ws.X, c.N, c.w->pre_w, c.w->pre_b, c.w->pre_bf, p.NO, p.table_groups, ws.NT, ne};
+  }
+
+  // The paired prelude (ForwardPlan::paired), two launches on the launch stream, each holding the blocks of two
+  // independent kernels: A = the closed-form order beside the node embedding, B = the wave ranges and segment
+  // positions beside the first node table. Each role reads only what earlier launches wrote.
+  int launch_paired() {
+    const PreludeGrids& g = p.grids;
+    const FullyPrepArgs fa = fully_args();
+    const NodeRowsArgs na = rows_args(ROWS_EMBED, -1, false);
+    hipLaunchKernelGGL(prelude_a_kernel, dim3((unsigned)(g.a_split + g.rows_blocks)), dim3(256),
+                       prelude_a_lds_bytes(na), st, fa, na, g.a_split, g.a_gx);
+    PEMP_LAUNCH_CHECK();
+    const EdgeRangesArgs ra = ranges_args();
+    const NodeTableArgs ta = table_args();
+    with_prec(p.table_prec, [&](auto P) {
+      hipLaunchKernelGGL(prelude_b_kernel<decltype(P)::value>, dim3((unsigned)(g.b_split + g.table_blocks)), dim3(256),
+                         0, st, ra, ta, g.b_split);
+    });
+    PEMP_LAUNCH_CHECK();
+    return PEMP_OK;
+  }
+
+  // x for the next stage (mode) + heads when slot >= 0, then the node table when `table`
+  int node_step(int mode, bool table, int slot, bool dup) {
+    const pemp_mpn_weights& w = *c.w;
+    const int64_t N = c.N;
+    const int T = p.T, J = p.J;
+    // middle steps of the attention model (update block in the edge pass, no heads): the node update runs inside the
+    // node-table launch (node_table_kernel<PREC, 1, true>) instead of a launch of its own
+    if (mode == ROWS_SUM && table && slot < 0 && p.sum_in_table) {
+      NodeTableArgs ta{ws.X, N, w.pre_w, w.pre_b, w.pre_bf, p.NO, p.table_groups, ws.NT, ne, ws.agg, ws.seg, T,
+                       w.upd_b};
+      ProfScope prof("node_update_table", st);
+      with_prec(p.table_prec, [&](auto P) {
+        hipLaunchKernelGGL((node_table_kernel<decltype(P)::value, 1, true>), dim3(p.table_grid1), dim3(256), 0, st, ta);
+      });
+      PEMP_LAUNCH_CHECK();
+      return PEMP_OK;
+    }
+    if (mode == NODE_UPDATE_MLP && w.upd_mlp.n_layers > 0) {   // hierarchical update MLP (dense-folded)
+      NodeMlpArgs ma{ws.agg, ws.seg, T, N, w.upd_mlp, nmlp_max_out(w.upd_mlp), ws.X, ne};
+      ProfScope prof("node_update", st);
+      hipLaunchKernelGGL(node_mlp_kernel, dim3(p.node_grid), dim3(256), nmlp_lds_bytes(T, w.upd_mlp), st, ma);
+      PEMP_LAUNCH_CHECK();
+      mode = ROWS_NONE;
+    } else if (mode == NODE_UPDATE_MLP) {                      // update MLP on non-linear aggregates
+      NodeUpdateArgs ua{ws.agg, ws.seg, T, N, w.upd_w, w.upd_b, ws.X, ne};
+      ProfScope prof("node_update", st);
+      hipLaunchKernelGGL(node_update_kernel, dim3(p.node_grid, 4), dim3(64 * UPD_WAVES), 0, st, ua);
+      PEMP_LAUNCH_CHECK();
+      mode = ROWS_NONE;
+    }
+    const NodeRowsArgs na = rows_args(mode, slot, dup);
     if (na.mode != ROWS_NONE || na.node_out) {
-      ProfScope prof(mode == ROWS_EMBED ? "node_embed" : "node_update", nst);
-      hipLaunchKernelGGL(node_rows_kernel, dim3(p.node_grid), dim3(256), node_rows_lds_bytes(na), nst, na);
+      ProfScope prof(mode == ROWS_EMBED ? "node_embed" : "node_update", st);
+      hipLaunchKernelGGL(node_rows_kernel, dim3(p.node_grid), dim3(256), node_rows_lds_bytes(na), st, na);
       PEMP_LAUNCH_CHECK();
     }
     if (slot >= 0 && !p.fused_heads) {
       for (int k = 0; k < (dup ? 2 : 1); ++k) {
         int r2;
         if ((r2 = rows_mlp("heads", w.node_head, ws.X + 64, 128, N, c.node_logits + (int64_t)(slot + k) * N, 1, nullptr,
-                           0, nst)))
+                           0, st)))
           return r2;
         if ((r2 = rows_mlp("heads", w.class_head, ws.X + 64, 128, N, c.class_logits + (int64_t)(slot + k) * N * J, J,
-                           nullptr, 0, nst)))
+                           nullptr, 0, st)))
           return r2;
       }
     }
     if (table) {
-      NodeTableArgs ta{ws.X, N, w.pre_w, w.pre_b, w.pre_bf, p.NO, p.table_groups, ws.NT, ne};
-      ProfScope prof("node_table", nst);
+      const NodeTableArgs ta = table_args();
+      ProfScope prof("node_table", st);
       with_prec(p.table_prec, [&](auto P) {
-        hipLaunchKernelGGL(node_table_kernel<decltype(P)::value>, dim3(p.table_grid), dim3(256), 0, nst, ta);
+        hipLaunchKernelGGL(node_table_kernel<decltype(P)::value>, dim3(p.table_grid), dim3(256), 0, st, ta);
       });
       PEMP_LAUNCH_CHECK();
-      if (p.ept) {   // columns 0..127 of the table: the per-type node terms (zero rows in pre_w)
-        NodeEptArgs xa{ws.X, c.node_types, p.tstride, T, N, w.ept_l1_w, w.ept_l1_b, w.ept_l2_w, w.ept_l2_b,
-                       w.ept_o1_w, w.ept_o2_w, ws.NT, p.NO,
-                       c.desc->precision == PEMP_PREC_F16X3 ? dom<2>() : 1.0f, ne};
-        hipLaunchKernelGGL(node_ept_kernel, dim3(p.node_grid), dim3(256), 0, nst, xa);
-        PEMP_LAUNCH_CHECK();
-      }
+      return launch_ept();
     }
+    return PEMP_OK;
+  }
+
+  // EDGE_MLP per_type: columns 0..127 of the table, the per-type node terms (zero rows in pre_w)
+  int launch_ept() {
+    if (!p.ept) return PEMP_OK;
+    const pemp_mpn_weights& w = *c.w;
+    NodeEptArgs xa{ws.X, c.node_types, p.tstride, p.T, c.N, w.ept_l1_w, w.ept_l1_b, w.ept_l2_w, w.ept_l2_b,
+                   w.ept_o1_w, w.ept_o2_w, ws.NT, p.NO,
+                   c.desc->precision == PEMP_PREC_F16X3 ? dom<2>() : 1.0f, ne};
+    hipLaunchKernelGGL(node_ept_kernel, dim3(p.node_grid), dim3(256), 0, st, xa);
+    PEMP_LAUNCH_CHECK();
     return PEMP_OK;
   }
 
@@ -4408,7 +4497,7 @@ struct Forward {
 #ifdef PEMP_STAMPS
     ea.stamps = it == g_diag_stamp_pass ? g_diag_stamps : nullptr;
 #endif
-    if (it == 0 && p.fused_first) {   // embedding + pass 0 in one launch (the side stream has joined: it reads NT)
+    if (it == 0 && p.fused_first) {   // embedding + pass 0 in one launch (it reads the first node table)
       ea.ea = c.edge_attr; ea.A = d.edge_attr_dim;
       ea.emb_img = c.w->edge_img + embed_image_offset(d, *c.w);
       ProfScope prof("edge_first", st);
@@ -4434,23 +4523,23 @@ struct Forward {
   }
 
   // The prelude. The edge prelude (order, wave ranges, edge embedding) needs nothing the node embedding and the first
-  // node table produce (their 16-row grids leave most CUs idle). From SIDE_MIN_E edges on (ForwardPlan::side) those
-  // two go to a side stream, forked from and joined back into the launch stream, and the edge prelude stays on the
-  // launch stream: the step's critical path -- graph build -> order -> ranges -> embedding -> first pass -- then
-  // carries neither the fork's nor the join's cross-stream wait (the side chain, ~20 us, is done long before the
-  // ~60 us prelude). Without a side stream the same launches go to the launch stream in the same order.
+  // node table produce (their 16-row grids leave most CUs idle). In the paired form (ForwardPlan::paired,
+  // launch_paired) the two chains share two launches. The separate form is the same kernels in launches of their
+  // own, one after the other. Everything is on the launch stream: a side stream for the node chain cost a 7 us fork
+  // and a 13 us join wait in front of the first pass.
   int prelude() {
     int rc;
-    SideFork side(p.side ? side_stream_for(st) : nullptr, st);
-    nst = side.stream();
+    if (p.paired) {   // (T = 1 model steps and the other shapes without a fused first pass: the embedding follows B)
+      if (!(rc = launch_paired()) && !(rc = launch_ept())) rc = launch_embed();
+      return rc;
+    }
     // node embedding + node table of the first iteration (or, without iterations, the heads on the embedding);
     // embedding widths > 128 would not fit the node step's LDS rows: separate launch
     rc = p.fused_embed ? PEMP_OK
-                       : rows_mlp("node_embed", c.w->node_emb, c.x, c.desc->node_in_dim, c.N, ws.X, 128, ws.X + 64, 128, nst);
+                       : rows_mlp("node_embed", c.w->node_emb, c.x, c.desc->node_in_dim, c.N, ws.X, 128, ws.X + 64, 128, st);
     if (!rc) rc = node_step(p.fused_embed ? ROWS_EMBED : ROWS_NONE, p.steps > 0, p.steps > 0 ? -1 : 0, false);
-    nst = st;
     if (!rc && !(rc = launch_order()) && !(rc = launch_ranges())) rc = launch_embed();
-    return rc;   // (leaving the scope joins the side stream, on the error paths too)
+    return rc;
   }
 
   int run() {
@@ -4515,7 +4604,7 @@ extern "C" int pemp_mpn_forward_fully(const pemp_mpn_desc* desc, const pemp_mpn_
 
 // ---- HIP graphs of the capacity-mode forward ------------------------------------------------------------------
 // A capacity-mode forward's launches depend only on its arguments (pointers, capacities, descriptor, weight set),
-// never on the batch's counts, so the whole sequence (~15 launches, its side-stream fork and join included) is
+// never on the batch's counts, so the whole sequence (~13 launches, all on one stream) is
 // captured into a HIP graph the second time the same arguments come (the first time they launch directly: one-off
 // argument sets never pay a capture) and replayed with one launch from then on -- a serving loop whose allocator
 // hands back the same buffers every step. Keyed by the bytes of every argument; a small LRU.
@@ -4781,6 +4870,17 @@ extern "C" int pemp_mpn_order_layout(const pemp_mpn_desc* desc, int64_t N, int64
 }
 
 extern "C" size_t pemp_mpn_fused_first_lds_bytes(void) { return edge_first_lds_bytes(); }
+
+extern "C" int pemp_mpn_prelude_grids(int64_t N, int64_t E, int B, int T, int nmax, int edge_grid, int cus,
+                                      int32_t* out8) {
+  PEMP_CHECK_ARG(out8 && N >= 0 && E >= 0 && B >= 0 && B <= FULLY_MAXB && T >= 1 && T <= MAXT && nmax >= 0 &&
+                     nmax <= FULLY_MAXN && edge_grid >= 1 && cus >= 1,
+                 "pemp_mpn_prelude_grids: bad args");
+  const PreludeGrids g = prelude_grids(N, E, B, T, nmax, edge_grid, cus);
+  static_assert(sizeof(PreludeGrids) == 8 * sizeof(int32_t), "eight ints");
+  memcpy(out8, &g, sizeof(g));
+  return PEMP_OK;
+}
 
 extern "C" size_t pemp_mpn_edge_image_floats(const pemp_mpn_desc* desc, const pemp_mpn_weights* w) {
   if (!desc || !w || desc->num_types < 1 || desc->num_types > MAXT) return 0;

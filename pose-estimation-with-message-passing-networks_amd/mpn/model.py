@@ -250,6 +250,10 @@ class NodeClassificationMPNSimple(nn.Module):
         # in a forward the library profiler records, True there too, False never (two launches, the same bits);
         # pemp.h PEMP_MPN_TWO_LAUNCH_FIRST / PEMP_MPN_FUSED_FIRST_PROFILED
         self.fuse_first_pass = None
+        # the prelude of a fully-graph forward as two paired launches (edge order beside node embedding, wave ranges
+        # beside the first node table); False keeps the four launches of their own (the same bits);
+        # pemp.h PEMP_MPN_SEPARATE_PRELUDE
+        self.paired_prelude = True
         # training mode only (eval never reads it): True runs the edge update mlp_edge(cat([x[dst], x[src], ef])) as
         # the fused MFMA operator with its own backward (mpn/train.py edge_update); False (the default) keeps the
         # gather + concatenation + torch GEMM form, whose numerics the training tests pin
@@ -291,13 +295,14 @@ class NodeClassificationMPNSimple(nn.Module):
 
     def _first_flag(self):
         f = self.fuse_first_pass
-        return 0 if f is None else _lib.MPN_FUSED_FIRST_PROFILED if f else _lib.MPN_TWO_LAUNCH_FIRST
+        first = 0 if f is None else _lib.MPN_FUSED_FIRST_PROFILED if f else _lib.MPN_TWO_LAUNCH_FIRST
+        return first | (0 if self.paired_prelude else _lib.MPN_SEPARATE_PRELUDE)
 
     def _descriptor(self, A, C, t_stride, counts_in_off=False):
         """byref of the library descriptor for edge_attr width A, node width C and this node_types stride, built when
-        one of those, the precision or fuse_first_pass changes (self._n_rec with it); with counts_in_off the
+        one of those, the precision, fuse_first_pass or paired_prelude changes (self._n_rec with it); with counts_in_off the
         PEMP_MPN_COUNTS_IN_OFFSETS one, cached on its own. (The struct itself is the byref's ``_obj``.)"""
-        dkey = (A, C, self.precision, t_stride, self.fuse_first_pass)
+        dkey = (A, C, self.precision, t_stride, self.fuse_first_pass, self.paired_prelude)
         ent = self._descs.get(counts_in_off)
         if ent is None or ent[0] != dkey:
             steps, aux = self.edge_steps, self.aux_loss_steps
