@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PEMP_ABI_VERSION 23
+#define PEMP_ABI_VERSION 24
 
 enum {
   PEMP_OK = 0,
@@ -166,15 +166,14 @@ int pemp_fully_graph_build(const int32_t* n_det, int B, const int64_t* det_xyt, 
  * e_cap rows and edge_index 2 * e_cap entries written as a contiguous [2, E] array. When the batch
  * exceeds either capacity nothing is written: the caller compares its read-back totals with the
  * capacities and then calls pemp_fully_graph_build with exact sizes. */
-/* mode | PEMP_BUILD_WRITE_COUNTS (capacity mode): node_off holds B + 4 entries and the build also writes the batch's
- * (N, E, overflow) at node_off[B + 1 .. B + 3] -- (0, 0, 1) for a batch past a capacity -- for
- * pemp_mpn_forward_fully_cap with PEMP_MPN_COUNTS_IN_OFFSETS */
-#define PEMP_BUILD_WRITE_COUNTS 0x100
+/* node_off (when given) holds B + 4 entries here: behind the B + 1 offsets the build writes the batch's
+ * (N, E, overflow) at node_off[B + 1 .. B + 3] -- (0, 0, 1) for a batch past a capacity -- which
+ * pemp_mpn_forward_fully_cap reads */
 int pemp_fully_graph_build_cap(const int32_t* n_det, int B, const int64_t* det_xyt, const float* det_scores, int cap,
                                const float* features, int C, const float* tagmaps, int F, int J, int H, int W,
                                int64_t n_cap, int64_t e_cap, float norm_factor, int mode, float* x,
                                int64_t* joint_det, float* joint_scores, int64_t* batch_index, float* joint_tags,
-                               int64_t* edge_index, float* edge_attr, int64_t* node_off /*[B+1] or NULL*/,
+                               int64_t* edge_index, float* edge_attr, int64_t* node_off /*[B+4] or NULL*/,
                                void* stream);
 
 /* Fully connected graph per image: all (i,j), i != j, sorted by (src,dst), node-offset per image.
@@ -184,17 +183,9 @@ int pemp_fully_graph(const int64_t* node_off, const int64_t* edge_off, int B, in
 
 /* knn graph per image (k nearest by squared integer distance, ties by node index; k+1 queried
  * with self removed), symmetrised and sorted by (src,dst).
- * Stage 1 (count): writes edge_count[b] (device int64 [B]). Host then sizes E and edge_off.
- * Stage 2 (emit): writes edge_index with per-image offsets edge_off (device [B+1]).
- * node_off_host: HOST [B+1] copy of node_off (grid sizing). Workspace is shared by both stages. */
+ * node_off_host: HOST [B+1] copy of node_off (grid sizing). */
 size_t pemp_knn_workspace_size(const int64_t* node_off_host, int B);
-int pemp_knn_graph_count(const int64_t* joint_det, const int64_t* node_off, const int64_t* node_off_host,
-                         int B, int k, void* workspace, size_t workspace_bytes, int64_t* edge_count,
-                         void* stream);
-int pemp_knn_graph_emit(const int64_t* node_off, const int64_t* node_off_host, int B,
-                        const int64_t* edge_off, int64_t e_total, void* workspace,
-                        size_t workspace_bytes, int64_t* edge_index, void* stream);
-/* Both stages in one call, no host round trip between them (replaces ConstructGraph.py:363-368 +
+/* The whole graph in one call, no host round trip in the middle (replaces ConstructGraph.py:363-368 +
  * the count read-back): adjacency, per-image counts, their device scan and the emit, back to back.
  * edge_buf: device int64 [2 * e_cap], e_cap >= sum_b min(n_b (n_b - 1), 2 k n_b) (checked); the graph
  * is its leading [2, E] block (sources at 0, destinations at E). e_total_host: mapped host int32
@@ -451,10 +442,6 @@ typedef struct pemp_mpn_desc {
 } pemp_mpn_desc;
 
 #define PEMP_MPN_PREPARED 1
-/* pemp_mpn_forward_fully_cap only: node_off holds B + 4 entries, the last three the batch's (N, E, overflow) as
- * pemp_fully_graph_build_cap wrote them with PEMP_BUILD_WRITE_COUNTS: the forward reads them instead of deriving
- * them from n_det in a launch of its own */
-#define PEMP_MPN_COUNTS_IN_OFFSETS 2
 /* The edge embedding and the first pass always as two launches. Without it the published composed f16x3 attention
  * model (steps >= 2, first pass not recorded, prebuilt edge_img) runs them as one; the logits are the same bits
  * either way. For A/B runs and tests. */
@@ -503,9 +490,9 @@ int pemp_mpn_forward_fully(const pemp_mpn_desc* desc, const pemp_mpn_weights* we
 
 /* Capacity mode of pemp_mpn_forward_fully: queued right behind pemp_fully_graph_build_cap, before the host has the
  * detection counts (replaces the host read-back at ConstructGraph.py:1174,1178 ahead of the MPN). x / edge_attr /
- * node_types (= joint_det + 2, stride 3) / node_off are that build's capacity buffers (n_cap rows, e_cap edges);
- * n_det is the detection's device count array ([B], det_cap detections per image at most). The batch's N and E
- * are derived on the device; the logits are written compactly for those (edge row r at r * E, node / class row r
+ * node_types (= joint_det + 2, stride 3) / node_off are that build's capacity buffers (n_cap rows, e_cap edges;
+ * node_off [B + 4], the batch's (N, E, overflow) read at node_off[B + 1 .. B + 3]); n_det is the detection's device
+ * count array ([B], det_cap detections per image at most). The batch's N and E stay on the device; the logits are written compactly for those (edge row r at r * E, node / class row r
  * at r * N), inside arrays sized for the capacities. A batch past any capacity (the capacity build then wrote
  * nothing) runs as an empty forward and writes no logits: the caller, which reads the counts back anyway, re-runs
  * the exact path. PEMP_ERR_UNSUPPORTED for models whose node MLPs are not fused (node embedding, heads) or
@@ -520,8 +507,7 @@ int pemp_mpn_forward_fully_cap(const pemp_mpn_desc* desc, const pemp_mpn_weights
  * One batch of the inference path in one call (no reference counterpart: a serving entry for a repeated batch
  * shape; construct_graph_start's capacity mode, ConstructGraph.py:1161-1209 + 206-231 + 376-381 and
  * NodeClassificationMPNSimple.py:62-97, takes it): pemp_detect (stages ALL, the counts stored into n_det_host) +
- * pemp_fully_graph_build_cap (PEMP_BUILD_WRITE_COUNTS) + pemp_mpn_forward_fully_cap (PEMP_MPN_COUNTS_IN_OFFSETS;
- * desc == NULL: none), queued on one stream. The arguments that repeat from batch to batch live in a plan that
+ * pemp_fully_graph_build_cap + pemp_mpn_forward_fully_cap (desc == NULL: none), queued on one stream. The arguments that repeat from batch to batch live in a plan that
  * pemp_step_layout completes once; every output lives in ONE caller buffer of plan.bytes bytes at the offsets it
  * computes (off[PEMP_STEP_*], 256-byte aligned):
  *   DET [B, det_cap, 3] i64, DSC [B, det_cap] f32, NDET [B] i32 (pemp_detect's outputs); X [n_cap, C],
@@ -533,7 +519,7 @@ int pemp_mpn_forward_fully_cap(const pemp_mpn_desc* desc, const pemp_mpn_weights
  * leaves the build's and the forward's outputs unwritten (the caller re-runs the exact path, as with the capacity
  * calls). Returns PEMP_ERR_UNSUPPORTED when only the forward was refused (pemp_mpn_forward_fully_cap's conditions;
  * the detection and the build are queued). Workspaces: det_workspace >= pemp_detect_workspace_size, mpn_workspace
- * >= pemp_mpn_workspace_size(desc with PEMP_MPN_COUNTS_IN_OFFSETS, n_cap, e_cap); both stream-ordered like the
+ * >= pemp_mpn_workspace_size(desc, n_cap, e_cap); both stream-ordered like the
  * outputs. scoremaps: [B, J, H, W] f32, or a pemp_proj_maps* when projected != 0 (pemp_detect_projected). */
 enum {
   PEMP_STEP_DET = 0, PEMP_STEP_DSC, PEMP_STEP_NDET, PEMP_STEP_X, PEMP_STEP_JDET, PEMP_STEP_JSC, PEMP_STEP_BIDX,
@@ -549,7 +535,7 @@ typedef struct pemp_step_plan {
   int32_t C, F, A, mode;        /* F = 0: no tagmaps; A: edge_attr columns of mode (PEMP_EF_*) */
   float norm_factor;
   int64_t n_cap, e_cap;
-  /* forward (desc NULL: none); desc->flags must hold PEMP_MPN_COUNTS_IN_OFFSETS */
+  /* forward (desc NULL: none) */
   const pemp_mpn_desc* desc;
   const pemp_mpn_weights* weights;
   void* mpn_workspace;
@@ -652,7 +638,7 @@ int pemp_mpn_status(const pemp_mpn_desc* desc, int64_t N, int64_t E, const void*
 /* Opt-in profiler: while enabled, hipEvents are recorded on the launch stream around every kernel
  * whose label contains `filter` ("*" = all, NULL or "" = off). pemp_prof_report synchronises those
  * events and writes "label count total_ms" lines into buf (returns the full length), then resets.
- * Labels: detect_nms, detect_top, detect_emit, pack_nodes, fully_graph, edge_features, knn_adj, knn_emit, score_graph,
+ * Labels: detect_nms, detect_top, detect_emit, pack_nodes, fully_graph, edge_features, score_graph,
  * mpn_prepare (the sorting prepare; the closed forms report under mpn_prepare_fully, mpn_prepare_sym and
  * mpn_prepare_knn, so the filter "mpn_prepare" catches all four), node_embed, edge_embed, node_table, edge_step, edge_step_head, node_update, heads, seg_aggr_fwd,
  * seg_aggr_bwd, seg_rows_sum, edge_mlp_fwd, edge_mlp_bwd, edge_mlp_tree. Model shapes off the published one report their fall-back kernels under labels of

@@ -9,11 +9,10 @@ import os
 
 LIB_PATH = os.environ.get("PEMP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc",
                                                      "libpemp.so")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 ERR_INVALID_ARG, ERR_HIP, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -3, -4
-BUILD_WRITE_COUNTS = 0x100          # pemp.h PEMP_BUILD_WRITE_COUNTS
-MPN_PREPARED, MPN_COUNTS_IN_OFFSETS, MPN_TWO_LAUNCH_FIRST, MPN_FUSED_FIRST_PROFILED = 1, 2, 4, 8   # pemp.h PEMP_MPN_*
+MPN_PREPARED, MPN_TWO_LAUNCH_FIRST, MPN_FUSED_FIRST_PROFILED = 1, 4, 8   # pemp.h PEMP_MPN_*
 MPN_SEPARATE_PRELUDE = 16
 
 c_i32, c_i64, c_f32, c_sz, c_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
@@ -84,8 +83,6 @@ SIGNATURES = {
                                            c_i64, c_i64, c_f32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pemp_fully_graph": (c_i32, [c_p, c_p, c_i32, c_i64, c_p, c_p]),
     "pemp_knn_workspace_size": (c_sz, [c_p, c_i32]),
-    "pemp_knn_graph_count": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_p, c_sz, c_p, c_p]),
-    "pemp_knn_graph_emit": (c_i32, [c_p, c_p, c_i32, c_p, c_i64, c_p, c_sz, c_p, c_p]),
     "pemp_knn_graph_build": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_p, c_sz, c_i64, c_p, c_p, c_p, c_i32, c_p,
                                      c_i32, c_f32, c_i32, c_p, c_p]),
     "pemp_feature_knn_workspace_size": (c_sz, [c_p, c_i32]),

@@ -749,7 +749,7 @@ struct FusedGraphArgs {
   float norm;
   int64_t n_total, e_total;   // exact totals, or capacities (capacity mode)
   int capacity;               // 1: totals come from n_det on the device; nothing is written if they exceed
-  int write_counts;           // capacity mode, PEMP_BUILD_WRITE_COUNTS: (N, E, overflow) at node_off_out[B + 1 ..]
+  int write_counts;           // capacity mode with node_off_out: (N, E, overflow) at node_off_out[B + 1 ..]
   int node_blocks;
   float *x, *jsc, *jtag, *edge_attr;
   int64_t *jdet, *bidx, *ei;
@@ -950,10 +950,7 @@ static int fully_graph_build(const int32_t* n_det, int B, const int64_t* det_xyt
                  "pemp_fully_graph_build: bad shape (B must be in [1, %d])", FUSED_MAXB);
   PEMP_CHECK_ARG(!tagmaps || (joint_tags && F > 0 && F <= C), "pemp_fully_graph_build: tags need F in [1, C]");
   PEMP_CHECK_ARG(e_total == 0 || (edge_index && edge_attr), "pemp_fully_graph_build: null edge outputs");
-  const int write_counts = (mode & PEMP_BUILD_WRITE_COUNTS) ? 1 : 0;
-  mode &= ~PEMP_BUILD_WRITE_COUNTS;
-  PEMP_CHECK_ARG(!write_counts || (capacity && node_off_out),
-                 "pemp_fully_graph_build: PEMP_BUILD_WRITE_COUNTS needs the capacity build and node_off");
+  const int write_counts = capacity && node_off_out;   // (N, E, overflow) after the offsets: node_off holds B + 4
   const int A = ef_width(mode, J);
   if (A < 0) { set_error("pemp_fully_graph_build: unknown edge feature mode %d", mode); return PEMP_ERR_INVALID_ARG; }
   if (const int rc = ef_tag_check(mode, tagmaps, F, "pemp_fully_graph_build")) return rc;
@@ -1265,56 +1262,6 @@ extern "C" size_t pemp_knn_workspace_size(const int64_t* node_off_host, int B) {
   size_t bytes = 0;
   knn_carve(nullptr, node_off_host, B, &bytes);
   return bytes;
-}
-
-extern "C" int pemp_knn_graph_count(const int64_t* joint_det, const int64_t* node_off, const int64_t* node_off_host,
-                                    int B, int k, void* workspace, size_t workspace_bytes, int64_t* edge_count,
-                                    void* stream) {
-  PEMP_CHECK_ARG(joint_det && node_off && node_off_host && workspace && edge_count && B > 0 && k >= 1,
-                 "pemp_knn_graph_count: bad args");
-  size_t need = 0;
-  knn_carve(nullptr, node_off_host, B, &need);
-  if (workspace_bytes < need) {
-    set_error("pemp_knn_graph_count: workspace %zu < %zu", workspace_bytes, need);
-    return PEMP_ERR_WORKSPACE;
-  }
-  const KnnWs w = knn_carve(workspace, node_off_host, B, nullptr);
-  const hipStream_t st = as_stream(stream);
-  const size_t words = knn_words(node_off_host, B, nullptr);
-  hipLaunchKernelGGL(knn_matoff_kernel, dim3(1), dim3(64), 0, st, node_off, B, w.mat_off);
-  PEMP_LAUNCH_CHECK();
-  PEMP_HIP(hipMemsetAsync(w.adj, 0, words * sizeof(unsigned long long), st));
-  PEMP_HIP(hipMemsetAsync(w.adjt, 0, words * sizeof(unsigned long long), st));
-  const int64_t n_total = node_off_host[B];
-  if (n_total > 0) {
-    ProfScope prof("knn_adj", st);
-    hipLaunchKernelGGL(knn_adj_kernel, dim3((unsigned)((n_total + 3) / 4)), dim3(256), 0, st,
-                       KnnDist{joint_det, nullptr, nullptr}, node_off, B, n_total, k + 1, w.mat_off, w.adj, w.adjt);
-    PEMP_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(knn_count_kernel, dim3(B), dim3(256), 0, st, node_off, B, w.mat_off, w.adj, w.adjt, edge_count);
-  PEMP_LAUNCH_CHECK();
-  return PEMP_OK;
-}
-
-extern "C" int pemp_knn_graph_emit(const int64_t* node_off, const int64_t* node_off_host, int B,
-                                   const int64_t* edge_off, int64_t e_total, void* workspace,
-                                   size_t workspace_bytes, int64_t* edge_index, void* stream) {
-  PEMP_CHECK_ARG(node_off && node_off_host && edge_off && workspace && edge_index && B > 0 && e_total >= 0,
-                 "pemp_knn_graph_emit: bad args");
-  size_t need = 0;
-  knn_carve(nullptr, node_off_host, B, &need);
-  if (workspace_bytes < need) {
-    set_error("pemp_knn_graph_emit: workspace %zu < %zu", workspace_bytes, need);
-    return PEMP_ERR_WORKSPACE;
-  }
-  const KnnWs w = knn_carve(workspace, node_off_host, B, nullptr);
-  if (e_total == 0) return PEMP_OK;
-  ProfScope prof("knn_emit", as_stream(stream));
-  hipLaunchKernelGGL(knn_emit_kernel, dim3(B), dim3(1024), 0, as_stream(stream), node_off, B, w.mat_off, w.adj,
-                     w.adjt, edge_off, e_total, e_total, edge_index);
-  PEMP_LAUNCH_CHECK();
-  return PEMP_OK;
 }
 
 // The whole knn graph without a host round trip in the middle: adjacency, per-image counts, their scan

@@ -3220,40 +3220,6 @@ static StagePlan node_image_plan(const pemp_mpn_weights& w) {
 constexpr int FULLY_MAXB = 64;      // images per batch
 constexpr int FULLY_MAXN = 2048;    // nodes per image (LDS lists)
 constexpr int FULLY_PARTS = 4;   // threads per (type, target) segment in fully_prepare_kernel
-// Capacity mode (pemp_mpn_forward_fully_cap): the batch's N = sum n_b and E = sum n_b (n_b - 1) from the detection
-// counts on the device, before the host has them. ne = (N, E, overflow); a batch past any capacity (an image over
-// the detection capacity, N > n_cap or E > e_cap: the capacity graph build wrote nothing) gets (0, 0, 1), and every
-// kernel of the forward then runs empty.
-__global__ __launch_bounds__(256) void cap_counts_kernel(const int32_t* __restrict__ n_det, int B, int det_cap,
-                                                         int64_t n_cap, int64_t e_cap, int64_t* __restrict__ ne) {
-  __shared__ long long sn[4], se[4];
-  __shared__ int sb[4];
-  long long n = 0, e = 0;
-  int bad = 0;
-  for (int b = threadIdx.x; b < B; b += 256) {
-    const long long c = n_det[b];
-    bad |= c < 0 || c > det_cap;
-    n += c;
-    e += c * (c > 0 ? c - 1 : 0);
-  }
-  for (int off = 32; off >= 1; off >>= 1) {
-    n += __shfl_xor(n, off);
-    e += __shfl_xor(e, off);
-    bad |= __shfl_xor(bad, off);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { sn[wave] = n; se[wave] = e; sb[wave] = bad; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    n = sn[0] + sn[1] + sn[2] + sn[3];
-    e = se[0] + se[1] + se[2] + se[3];
-    const bool over = (sb[0] | sb[1] | sb[2] | sb[3]) || n > n_cap || e > e_cap;
-    ne[0] = over ? 0 : n;
-    ne[1] = over ? 0 : e;
-    ne[2] = over ? 1 : 0;
-  }
-}
-
 struct FullyPrepArgs {
   const int64_t* node_off;          // [B + 1] device
   int B;
@@ -3997,12 +3963,12 @@ struct EdgeOrder {
   const KnnPrepArgs* knn = nullptr;   // KNN: the graph build's row lists (knn_prepare_kernel)
 };
 
-// capacity mode (pemp_mpn_forward_fully_cap): N and E are capacities; the device-side counts come first -- from the
-// capacity graph build (ne: PEMP_MPN_COUNTS_IN_OFFSETS) or from a launch of their own
+// capacity mode (pemp_mpn_forward_fully_cap): N and E are capacities; the device-side counts ne = (N, E, overflow) are
+// the capacity graph build's, after its node offsets. A batch past any capacity (an image over the detection
+// capacity, N > n_cap or E > e_cap: the build wrote nothing) has (0, 0, 1), and every kernel of the forward then
+// runs empty.
 struct CapMode {
-  const int32_t* n_det = nullptr;   // detections per image (device); NULL: an exact forward
-  int det_cap = 0;
-  const int64_t* ne = nullptr;
+  const int64_t* ne = nullptr;   // device; NULL: an exact forward
 };
 
 struct ForwardCall {
@@ -4233,16 +4199,11 @@ struct Forward {
   bool recorded(int it) const { return it >= p.steps - p.aux - 1; }
   bool last(int it) const { return it + 1 == p.steps; }
 
-  // what comes ahead of everything else on the launch stream: capacity mode's counts, and the two weight images
-  // where the caller did not prebuild them
+  // what comes ahead of everything else on the launch stream: the two weight images where the caller did not
+  // prebuild them
   int launch_setup() {
     const pemp_mpn_weights& w = *c.w;
-    ne = c.cap.ne ? c.cap.ne : c.cap.n_det ? reinterpret_cast<int64_t*>(ws.err + 8) : nullptr;
-    if (c.cap.n_det && !c.cap.ne) {
-      hipLaunchKernelGGL(cap_counts_kernel, dim3(1), dim3(256), 0, st, c.cap.n_det, c.order.B, c.cap.det_cap, c.N, c.E,
-                         reinterpret_cast<int64_t*>(ws.err + 8));
-      PEMP_LAUNCH_CHECK();
-    }
+    ne = c.cap.ne;
     // LDS image of the node-side MLPs: the caller's (pemp_mpn_node_image) or built here
     node_img = w.node_img;
     if (!node_img && (p.fused_heads || p.fused_embed)) {
@@ -4703,8 +4664,7 @@ extern "C" int pemp_mpn_forward_fully_cap(const pemp_mpn_desc* desc, const pemp_
     c.N = n_cap; c.E = e_cap; c.edge_logits = edge_logits; c.node_logits = node_logits; c.class_logits = class_logits;
     c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = s;
     c.order.kind = EdgeOrder::FULLY; c.order.node_off = node_off; c.order.B = B; c.order.nmax = det_cap;
-    c.cap.n_det = n_det; c.cap.det_cap = det_cap;
-    c.cap.ne = (desc->flags & PEMP_MPN_COUNTS_IN_OFFSETS) ? node_off + B + 1 : nullptr;
+    c.cap.ne = node_off + B + 1;
     return mpn_forward(c);
   };
   // PEMP_DEBUG_SYNC synchronises the device after every launch, which a capturing stream does not allow

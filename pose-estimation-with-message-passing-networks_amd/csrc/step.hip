@@ -102,14 +102,12 @@ extern "C" int pemp_step_fully_cap(const pemp_step_plan* p, const void* scoremap
   int64_t* noff = reinterpret_cast<int64_t*>(at(PEMP_STEP_NOFF));
   float* eattr = reinterpret_cast<float*>(at(PEMP_STEP_EATTR));
   rc = pemp_fully_graph_build_cap(n_det, p->B, det, dsc, p->det_cap, features, p->C, tagmaps, p->F ? p->F : 1, p->J,
-                                  p->H, p->W, p->n_cap, p->e_cap, p->norm_factor, p->mode | PEMP_BUILD_WRITE_COUNTS, x,
+                                  p->H, p->W, p->n_cap, p->e_cap, p->norm_factor, p->mode, x,
                                   jdet, reinterpret_cast<float*>(at(PEMP_STEP_JSC)),
                                   reinterpret_cast<int64_t*>(at(PEMP_STEP_BIDX)),
                                   p->F ? reinterpret_cast<float*>(at(PEMP_STEP_JTAGS)) : nullptr,
                                   reinterpret_cast<int64_t*>(at(PEMP_STEP_EIDX)), eattr, noff, stream);
   if (rc != PEMP_OK || !p->desc) return rc;
-  PEMP_CHECK_ARG(p->desc->flags & PEMP_MPN_COUNTS_IN_OFFSETS,
-                 "pemp_step_fully_cap: the forward reads the build's counts (desc flags PEMP_MPN_COUNTS_IN_OFFSETS)");
   float* lg = reinterpret_cast<float*>(at(PEMP_STEP_LOGITS));
   return pemp_mpn_forward_fully_cap(p->desc, p->weights, x, eattr, jdet + 2, p->n_cap, p->e_cap, n_det, p->det_cap,
                                     noff, p->B, lg, lg + p->nlog_off, lg + p->clog_off, p->mpn_workspace,

@@ -10,7 +10,7 @@ Host synchronisation: one count read-back after detection (the reference syncs a
 ``nonzero``), plus one more for knn graphs.
 """
 import ctypes
-import os
+import math
 import threading
 
 import numpy as np
@@ -20,22 +20,36 @@ from . import _lib
 from .frontend import ProjectedHeatmaps, ProjectedMaps
 
 _SCORE_BASED_K = 75        # ConstructGraph.py:280 (score_based_graph roots)
+# EDGE_FEATURES_TO_USE -> (mode code PEMP_EF_*, (a, b) of the edge_attr width A = a J + b: ef_width() of graph.hip)
 _EF_MODES = {
-    frozenset(["position", "connection_type"]): 0,
-    frozenset(["connection_type"]): 1,
-    frozenset(["nothing"]): 2,
-    frozenset(["position"]): 3,
-    frozenset(["position", "angle", "connection_type"]): 4,
-    frozenset(["position", "connection_type", "ae_normed"]): 5,   # associative-embedding modes,
-    frozenset(["ae"]): 6,                                         # ConstructGraph.py:337-357
-    frozenset(["ae_normed"]): 7,
-    frozenset(["ae_tracking_1"]): 8,
+    frozenset(["position", "connection_type"]): (0, (1, 2)),
+    frozenset(["connection_type"]): (1, (1, 0)),
+    frozenset(["nothing"]): (2, (0, 1)),
+    frozenset(["position"]): (3, (0, 2)),
+    frozenset(["position", "angle", "connection_type"]): (4, (1, 3)),
+    frozenset(["position", "connection_type", "ae_normed"]): (5, (1, 3)),   # associative-embedding modes,
+    frozenset(["ae"]): (6, (0, 1)),                                         # ConstructGraph.py:337-357
+    frozenset(["ae_normed"]): (7, (0, 1)),
+    frozenset(["ae_tracking_1"]): (8, (0, 1)),
 }
 _EF_TAG_MODES = (5, 6, 7, 8)
 
 
 def _align256(n):
     return (n + 255) // 256 * 256
+
+
+def _fully_edges(counts_l):
+    """Edges of the batch's fully graph: every ordered pair of an image's detections."""
+    return sum(c * (c - 1) for c in counts_l if c > 1)
+
+
+def _fits(counts_l, cap, n_cap, e_cap):
+    """(N, E) of a batch that fit the capacities its capacity build ran under, else None (it wrote nothing)."""
+    N, E = sum(counts_l), _fully_edges(counts_l)
+    if (max(counts_l) if counts_l else 0) > cap or N > n_cap or E > e_cap:
+        return None
+    return N, E
 
 
 def _tag_fully(edge_index, node_off, counts, joint_det):
@@ -61,72 +75,131 @@ def _tag_knn(edge_index, ws, offs, node_off, node_off_h):
     edge_index._pemp_knn = (ws, offs, node_off, node_off_h, edge_index._version)
 
 
-# the capacity graph build hands the capacity-mode MPN the batch's (N, E, overflow) (PEMP_BUILD_WRITE_COUNTS), so the
-# forward starts without a counting launch of its own; PEMP_NO_BUILD_COUNTS=1 restores that launch (A/B runs)
-_BUILD_COUNTS = not os.environ.get("PEMP_NO_BUILD_COUNTS")
-# a repeated fully-graph batch shape goes through the batch-step entry (pemp_step_fully_cap: one C call, one output
-# buffer; c2 0.17 -> 0.13 ms per step, profiles/r06_step_entry.md); PEMP_STEP_ENTRY=0 restores the three calls and
-# the per-output allocations (A/B runs)
-_STEP_ENTRY = _BUILD_COUNTS and os.environ.get("PEMP_STEP_ENTRY", "1") not in ("", "0")
+class _Call:
+    """What the host derives from one construct_graph call's inputs, filled once before the first launch: the detection
+    half here (ahead of the count buffer), the graph half in graph() (the generator's first step). src_obj is the dense
+    scoremaps or (proj) the pemp_proj_maps of a ProjectedHeatmaps; the features are dense (feats) or ProjectedMaps
+    (pmaps, pconv their feature_gather conv or None); the tags are absent, dense (tags) or projected (ptags)."""
+    __slots__ = ("L", "st", "dev", "B", "J", "H", "W", "proj", "src_obj", "src", "detect", "masks", "use_thr", "topk",
+                 "thr", "pool", "feats", "pmaps", "pconv", "divisor", "tags", "ptags", "C", "F", "A", "mode", "norm",
+                 "fully", "gkey", "counts_h")
+
+    def __init__(self, gc, L, st):
+        self.L, self.st = L, st
+        sm = gc.scoremaps
+        self.proj = isinstance(sm, ProjectedHeatmaps)   # the test front-end evaluated inside the detection
+        if self.proj:
+            self.src_obj = sm.c_struct()
+            self.src, self.detect = ctypes.addressof(self.src_obj), L.pemp_detect_projected
+        else:
+            if sm.dtype != torch.float32:
+                sm = sm.float()
+            self.src_obj = sm = sm.contiguous()
+            self.src, self.detect = sm.data_ptr(), L.pemp_detect
+        self.B, self.J, self.H, self.W = sm.shape
+        if self.J != gc.num_joints:
+            raise ValueError(f"scoremaps have {self.J} types, num_joints={gc.num_joints}")
+        if gc.mask_crowds and gc.masks is None:
+            raise TypeError("MASK_CROWDS is set but masks is None")   # reference: masks[batch] on None
+        self.masks = gc.masks.float().contiguous() if gc.mask_crowds else None
+        self.use_thr = use_thr = gc.detect_threshold is not None
+        self.topk, self.thr = (gc.hybrid_k, float(gc.detect_threshold)) if use_thr else (20, 0.0)
+        self.pool, self.dev = gc.pool_kernel_size, sm.device
+
+    def graph(self, gc, counts_h):
+        """The graph half: features, tags, edge-feature mode and the path's keys, with construct_graph's checks."""
+        J, H, W = self.J, self.H, self.W
+        feats, tags = gc.features, gc.tagmaps
+        pmaps = pconv = divisor = ptags = None
+        if isinstance(feats, ProjectedMaps):   # x sampled from the projected maps after the graph build
+            if feats.size != (H, W):
+                raise ValueError(f"ProjectedMaps size {feats.size} != scoremap size {(H, W)}")
+            pmaps = [m.float().contiguous() for m in feats.maps]
+            C, divisor = feats.shape[1], feats.divisor
+            pconv = feats.conv_params() if feats.gather is not None else None
+            feats = None
+        else:
+            if feats.dtype != torch.float32:
+                feats = feats.float()
+            feats = feats.contiguous()
+            C = feats.shape[1]
+        F = 1
+        if isinstance(tags, ProjectedHeatmaps):   # sampled at the detections after the build
+            if not tags.has_tags:
+                raise ValueError(f"ProjectedHeatmaps has {tags.outputs[0].shape[1]} channels: no tag channels")
+            ptags, tags, F = tags, None, tags.tag_dims
+        elif tags is not None:
+            tags = tags.float().contiguous()
+            F = math.prod(tags.shape[4:])
+        ef = _EF_MODES.get(frozenset(gc.edge_features_to_use))
+        if ef is None:
+            raise NotImplementedError(f"EDGE_FEATURES_TO_USE={gc.edge_features_to_use}")
+        mode, (a, b) = ef
+        if mode in _EF_TAG_MODES and tags is None and ptags is None:
+            raise TypeError(f"EDGE_FEATURES_TO_USE={gc.edge_features_to_use} needs tagmaps")
+        self.feats, self.pmaps, self.pconv, self.divisor, self.tags = feats, pmaps, pconv, divisor, tags
+        self.ptags, self.C, self.F, self.A, self.mode, self.counts_h = ptags, C, F, a * J + b, mode, counts_h
+        self.norm = float(max(W, H)) if gc.normalize_node_distance else 1.0
+        # (projected tags feeding the edge features: the generic path, which samples them before the features)
+        self.fully = (gc.mpn_graph_type == "fully" and self.B <= 1024
+                      and not (ptags is not None and mode in _EF_TAG_MODES))
+        self.gkey = (self.B, J, H, W, C, F, self.A, self.dev)
 
 
 class _StepPlan:
     """A pemp_step_plan (include/pemp.h) for one batch shape, capacity set and forward, with the workspaces it names
     kept alive; outputs() cuts one call's output buffer into construct_graph's tensors."""
 
-    def __init__(self, L, B, J, H, W, pool, use_thr, topk, thr, cap, det_ws, C, F, A, mode, norm, n_cap, e_cap, mi,
-                 proj):
-        p = _lib.PempStepPlan(B=B, J=J, H=H, W=W, pool_kernel=pool, use_threshold=int(use_thr), topk=topk,
-                              det_cap=cap, projected=int(proj), threshold=thr, det_workspace=det_ws.data_ptr(),
-                              det_workspace_bytes=det_ws.numel(), C=C, F=F, A=A, mode=mode, norm_factor=norm,
-                              n_cap=n_cap, e_cap=e_cap)
+    def __init__(self, c, cap, det_ws, n_cap, e_cap, mi):
+        F = c.F if c.tags is not None else 0
+        p = _lib.PempStepPlan(B=c.B, J=c.J, H=c.H, W=c.W, pool_kernel=c.pool, use_threshold=int(c.use_thr),
+                              topk=c.topk, det_cap=cap, projected=int(c.proj), threshold=c.thr,
+                              det_workspace=det_ws.data_ptr(), det_workspace_bytes=det_ws.numel(), C=c.C, F=F, A=c.A,
+                              mode=c.mode, norm_factor=c.norm, n_cap=n_cap, e_cap=e_cap)
         self.mi = mi                                     # (desc, folded weights, workspace, key): kept alive here
         if mi is not None:
             p.desc = ctypes.pointer(mi[0])
             p.weights = ctypes.pointer(mi[1].struct)
             p.mpn_workspace = mi[2].data_ptr()
             p.mpn_workspace_bytes = mi[2].numel()
-        if not L.pemp_step_layout(ctypes.byref(p)):
-            raise ValueError(L.pemp_last_error().decode())
+        if not c.L.pemp_step_layout(ctypes.byref(p)):
+            raise ValueError(c.L.pemp_last_error().decode())
         self.struct, self.ref, self.det_ws = p, ctypes.byref(p), det_ws
-        self.B, self.cap, self.C, self.F, self.A = B, cap, C, F, A
+        self.B, self.cap, self.C, self.F, self.A = c.B, cap, c.C, F, c.A
         self.off = [p.off[i] for i in range(_lib.STEP_NOUT)]
 
     def detections(self, flat):
-        """(det_xyt [B, cap, 3], det_scores [B, cap], n_det [B]) of the call that wrote flat."""
+        """(workspace, det_xyt [B, cap, 3], det_scores [B, cap], n_det [B]) of the call that wrote flat."""
         o, B, cap = self.off, self.B, self.cap
         i64, f32, i32 = flat.view(torch.int64), flat.view(torch.float32), flat.view(torch.int32)
-        return (i64.as_strided((B, cap, 3), (3 * cap, 3, 1), o[_lib.STEP_DET] // 8),
+        return (self.det_ws, i64.as_strided((B, cap, 3), (3 * cap, 3, 1), o[_lib.STEP_DET] // 8),
                 f32.as_strided((B, cap), (cap, 1), o[_lib.STEP_DSC] // 4),
                 i32.as_strided((B,), (1,), o[_lib.STEP_NDET] // 4))
 
-    def outputs(self, flat, counts_l, cap, tags, mpn, mi):
-        """construct_graph's 15-tuple from the call's buffer when the batch fit the capacities (else None); with a
-        forward, its queued logits are attached to edge_index for the model call to take."""
+    def outputs(self, flat, counts_l, mpn):
+        """(node arrays, edge_attr, edge_index) in the call's buffer when the batch fit the capacities (else None);
+        with a forward (mpn, this plan's mi), its queued logits are attached to edge_index for the model to take."""
         p = self.struct
-        N = sum(counts_l)
-        E = sum(c * (c - 1) for c in counts_l if c > 1)
-        if (max(counts_l) if counts_l else 0) > cap or N > p.n_cap or E > p.e_cap:
+        fit = _fits(counts_l, self.cap, p.n_cap, p.e_cap)
+        if fit is None:
             return None
+        N, E = fit
         o, C, F, A = self.off, self.C, self.F, self.A
         i64, f32 = flat.view(torch.int64), flat.view(torch.float32)
         x = f32.as_strided((N, C), (C, 1), o[_lib.STEP_X] // 4)
         joint_det = i64.as_strided((N, 3), (3, 1), o[_lib.STEP_JDET] // 8)
         joint_scores = f32.as_strided((N,), (1,), o[_lib.STEP_JSC] // 4)
         batch_index = i64.as_strided((N,), (1,), o[_lib.STEP_BIDX] // 8)
-        joint_tags = None
-        if tags is not None:   # [N, F] as the reference's tagmaps[b, type, y, x] rows: [N, *tags.shape[4:]] or [N]
-            joint_tags = f32.as_strided((N, F), (F, 1), o[_lib.STEP_JTAGS] // 4).view(
-                (N,) + tuple(tags.shape[4:]) if tags.dim() > 4 else (N,))
+        joint_tags = f32.as_strided((N, F), (F, 1), o[_lib.STEP_JTAGS] // 4) if F else None
         edge_index = i64.as_strided((2, E), (E, 1), o[_lib.STEP_EIDX] // 8)
         edge_attr = f32.as_strided((E, A), (A, 1), o[_lib.STEP_EATTR] // 4)
         node_off = i64.as_strided((self.B + 4,), (1,), o[_lib.STEP_NOFF] // 8)
         _tag_fully(edge_index, node_off, counts_l, joint_det)
-        if mpn is not None:
-            res = dict(buf=f32[o[_lib.STEP_LOGITS] // 4:], a1=p.nlog_off, a2=p.clog_off, n_rec=p.n_rec, key=mi[3])
+        if mpn is not None:   # the queued result as the model's _take_cap reads it
+            res = dict(buf=f32[o[_lib.STEP_LOGITS] // 4:], a1=p.nlog_off, a2=p.clog_off, n_rec=p.n_rec,
+                       key=self.mi[3])
             mpn._attach_cap(res, x, edge_attr, edge_index, joint_det, N, E)
-        return (x, edge_attr, edge_index, None, None, None, None, joint_det, None, None, None, joint_scores,
-                batch_index, None, joint_tags)
+        return (x, joint_det, joint_scores, batch_index, joint_tags), edge_attr, edge_index
 
 
 def get_graph_constructor(config, **kwargs):
@@ -193,12 +266,12 @@ class NaiveGraphConstructor:
 
     @classmethod
     def bind_mpn(cls, model):
-        """Capacity mode for the MPN (None unbinds): when construct_graph takes the capacity graph build
-        (pemp_fully_graph_build_cap, a repeated fully-graph batch shape), it also queues `model`'s forward on
-        those buffers (pemp_mpn_forward_fully_cap) before it reads the detection counts back, and tags its
-        output so that model(x, edge_attr, edge_index, node_types=joint_det[:, 2]) on that output returns the
-        queued logits instead of launching again. Any other call of the model -- another graph, an input or
-        weight edited in between, a batch that overflowed the capacities -- runs the exact forward."""
+        """Capacity mode for the MPN (None unbinds): when construct_graph takes the batch-step entry (a repeated
+        fully-graph batch shape with dense features, pemp_step_fully_cap), `model`'s forward is queued behind the
+        capacity build before the detection counts are read back, and the output is tagged so that model(x, edge_attr,
+        edge_index, node_types=joint_det[:, 2]) on it returns the queued logits instead of launching again. Any other
+        call of the model -- another graph, an input or weight edited in between, a batch that overflowed the
+        capacities -- runs the exact forward."""
         cls._bound_mpn = model
 
     @classmethod
@@ -295,12 +368,13 @@ class NaiveGraphConstructor:
                     mr=float(config.MATCHING_RADIUS), ir=float(config.INCLUSION_RADIUS), f64=f64,
                     gt=gt.float().contiguous(), fac=(fac if f64 else fac.float()).contiguous())
 
-    def _label_outputs(self, L, st, out, node_off, counts_l, B, H, W, dev):
+    def _label_outputs(self, c, out, node_off, counts_l):
         """construct_graph's tuple with slots 3, 4, 5, 8, 9, 10 and 13 filled as ConstructGraph.py:232-249 does:
         candidate pairs on the device (pemp_label_candidates), the matching on the host (pemp_label_assign; one
         read-back of the sparse list, one upload of the per-node results), the edge pass on the device
         (pemp_label_edges)."""
         lp = self._labels
+        L, st, B, H, W, dev = c.L, c.st, c.B, c.H, c.W, c.dev
         joint_det, edge_index = out[7], out[2]
         N, E = joint_det.shape[0], edge_index.shape[1]
         P, J = lp["gt"].shape[1], lp["gt"].shape[2]
@@ -335,8 +409,7 @@ class NaiveGraphConstructor:
                 NaiveGraphConstructor._label_cap = cap = max(NaiveGraphConstructor._label_cap, cap)
         m6 = lp["method"] == 6
         res_h = torch.empty(max(29 * N, 1), dtype=torch.uint8, pin_memory=True)
-        hp = res_h.data_ptr()
-        hb = host.data_ptr()
+        hp, hb = res_h.data_ptr(), host.data_ptr()
         rc = L.pemp_label_assign(B, P, J, hb, hb + o_tab, hb + o_rec, cap, node_off_h.ctypes.data, lp["method"],
                                  int(lp["neighbours"]), int(lp["background"]), mr, ir, hp + 16 * N, hp,
                                  hp + 8 * N if m6 else None, hp + 20 * N, hp + 24 * N if m6 else None, hp + 28 * N)
@@ -358,366 +431,291 @@ class NaiveGraphConstructor:
         return (out[0], out[1], out[2], edge_labels, node_labels, node_classes, None, out[7], label_mask,
                 label_mask_node, class_mask, out[11], out[12], node_persons, out[14])
 
-    # ------------------------------------------------------------------------------------
     def construct_graph(self):
         """ConstructGraph.py:46-68 (inference): the 15-tuple. = construct_graph_start().result()."""
         return self.construct_graph_start().result()
 
     def construct_graph_start(self):
         """The launch half of construct_graph (no reference counterpart): queues the detection and, with a capacity
-        hint, the graph build and the bound MPN, then returns a PendingGraph without waiting for the detection
-        counts. Its result() waits for them and returns construct_graph's 15-tuple. A caller with several batches
-        in flight (a server, bench.py) queues the next batch before it collects the previous one, so the host's
-        count wait overlaps its other work. A pending graph must be collected (result()) before another batch is
-        started on the same stream twice over (the library's scratch is per device and stream)."""
+        hint, the graph build and the bound MPN, then returns a PendingGraph without waiting for the detection counts.
+        Its result() waits for them and returns construct_graph's 15-tuple. A caller with several batches in flight (a
+        server, bench.py) queues the next batch before it collects the previous one, so the host's count wait overlaps
+        its other work. A pending graph must be collected (result()) before another batch is started on the same
+        stream twice over (the library's scratch is per device and stream)."""
         L = _lib.lib()
-        st = _lib.stream(self.device)
-        sm = self.scoremaps
-        if isinstance(sm, ProjectedHeatmaps):   # the test front-end evaluated inside the detection
-            self._proj = sm
-            self._proj_c = sm.c_struct()
-        else:
-            self._proj = None
-            if sm.dtype != torch.float32:
-                sm = sm.float()
-            sm = sm.contiguous()
-        B, J, H, W = sm.shape
-        if J != self.num_joints:
-            raise ValueError(f"scoremaps have {J} types, num_joints={self.num_joints}")
-        if self.mask_crowds:
-            if self.masks is None:
-                raise TypeError("MASK_CROWDS is set but masks is None")   # reference: masks[batch] on None
-            masks = self.masks.float().contiguous()
-        else:
-            masks = None
-        use_thr = self.detect_threshold is not None
-        topk = self.hybrid_k if use_thr else 20
-        thr = float(self.detect_threshold) if use_thr else 0.0
-        dev = sm.device
-
-        # ---- detection (pemp_detect): one read-back of the per-image counts ----
-        counts_ent = self._host_counts_take(L, dev, B)
-        gen = self._construct(L, st, sm, masks, B, J, H, W, use_thr, topk, thr, dev, counts_ent[2][:B])
-        pending = PendingGraph(self, gen, dev, counts_ent)
+        c = _Call(self, L, _lib.stream(self.device))
+        counts_ent = self._host_counts_take(L, c.dev, c.B)   # one read-back of the per-image counts (pemp_detect)
+        pending = PendingGraph(self, self._construct(c, counts_ent[2][:c.B]), c.dev, counts_ent)
         pending._step()                             # up to the count wait: everything is queued
         return pending
 
-    def _construct(self, L, st, sm, masks, B, J, H, W, use_thr, topk, thr, dev, counts_h):
-        # host-side preparation of the graph stage, before the first launch: with a capacity hint the detection,
-        # the graph build and the MPN are then queued back to back (no host gap between them on the GPU), and in a
-        # loop this preparation overlaps the previous batch's GPU work
-        feats = self.features
-        projected = isinstance(feats, ProjectedMaps)
-        if projected:      # x sampled from the projected maps after the graph build (pemp_gather_projected)
-            if feats.size != (H, W):
-                raise ValueError(f"ProjectedMaps size {feats.size} != scoremap size {(H, W)}")
-            pmaps = [m.float().contiguous() for m in feats.maps]
-            C = feats.shape[1]
-            pconv = feats.conv_params() if feats.gather is not None else None
-            feats = None
-        else:
-            if feats.dtype != torch.float32:
-                feats = feats.float()
-            feats = feats.contiguous()
-            C = feats.shape[1]
-        tags = self.tagmaps
-        proj_tags = None
-        if isinstance(tags, ProjectedHeatmaps):   # sampled at the detections after the build
-            if not tags.has_tags:
-                raise ValueError(f"ProjectedHeatmaps has {tags.outputs[0].shape[1]} channels: no tag channels")
-            proj_tags, tags = tags, None
-            F = proj_tags.tag_dims
-        elif tags is not None:
-            tags = tags.float().contiguous()
-            F = 1 if tags.dim() == 4 else int(np.prod(tags.shape[4:]))
-        else:
-            F = 1
-        mode = _EF_MODES.get(frozenset(self.edge_features_to_use))
-        if mode is None:
-            raise NotImplementedError(f"EDGE_FEATURES_TO_USE={self.edge_features_to_use}")
-        if mode in _EF_TAG_MODES and tags is None and proj_tags is None:
-            raise TypeError(f"EDGE_FEATURES_TO_USE={self.edge_features_to_use} needs tagmaps")
-        A = {0: J + 2, 1: J, 2: 1, 3: 2, 4: J + 3, 5: J + 3, 6: 1, 7: 1, 8: 1}[mode]
-        norm = float(max(W, H)) if self.normalize_node_distance else 1.0
-
-        # (projected tags feeding the edge features: the generic path, which samples them before the features)
-        fully = self.mpn_graph_type == "fully" and B <= 1024 and not (proj_tags is not None and mode in _EF_TAG_MODES)
-        gkey = (B, J, H, W, C, F, A, dev)
+    def _construct(self, c, counts_h):
+        """One of three stages, each a generator that yields once, where construct_graph_start returns. A stage prepares
+        everything on the host before its first launch, so its calls are queued back to back (no host gap between them
+        on the GPU), and in a loop this preparation overlaps the previous batch's GPU work."""
+        c.graph(self, counts_h)
         with NaiveGraphConstructor._mu:
             # with ground truth always the exact build: the labels need the host counts before they start anyway
-            hint = NaiveGraphConstructor._graph_hint.get(gkey) if fully and self._labels is None else None
+            hint = NaiveGraphConstructor._graph_hint.get(c.gkey) if c.fully and self._labels is None else None
             cap = NaiveGraphConstructor._cap
-        built = None
-        pending = None
-        launch_mpn = None
-        step = hint is not None and _STEP_ENTRY and not projected
-        if step:
-            # the batch-step entry: detection + capacity build + the bound MPN in one call, outputs in one buffer
-            n_cap, e_cap = hint
-            mpn = NaiveGraphConstructor._bound_mpn
+        if hint is None:
+            return (yield from self._exact_stage(c, cap))
+        if c.pmaps is None:
+            return (yield from self._step_stage(c, cap, hint))
+        return (yield from self._cap_stage(c, cap, hint))
+
+    def _step_stage(self, c, cap, hint):
+        """A repeated fully-graph batch shape with dense features, the batch-step entry: detection + capacity build +
+        the bound MPN in one call (pemp_step_fully_cap), every output in one buffer."""
+        n_cap, e_cap = hint
+        mpn = NaiveGraphConstructor._bound_mpn
+        bound = mpn is not None and c.J == getattr(mpn, "num_types", None) and getattr(mpn, "_cap_ok", True)
+        mi = mpn._cap_info(c.C, c.A, n_cap, e_cap, c.dev) if bound else None
+        plan = self._step_plan(c, cap, n_cap, e_cap, mi)
+        flat = torch.empty(plan.struct.bytes, dtype=torch.uint8, device=c.dev)
+        c.counts_h.fill(-1)
+        rc = c.L.pemp_step_fully_cap(plan.ref, c.src, _lib.ptr(c.masks), c.feats.data_ptr(), _lib.ptr(c.tags),
+                                     flat.data_ptr(), c.counts_h.ctypes.data, c.st)
+        if rc == _lib.ERR_UNSUPPORTED and mi is not None:
+            mpn._cap_ok = False     # the forward's conditions refused this model: the exact forward from now on
             mi = None
-            if mpn is not None and J == getattr(mpn, "num_types", None) and getattr(mpn, "_cap_ok", True):
-                mi = mpn._cap_info(C, A, n_cap, e_cap, dev)
-            plan = self._step_plan(L, dev, st, B, J, H, W, use_thr, topk, thr, cap, C, F if tags is not None else 0,
-                                   A, mode, norm, n_cap, e_cap, mi, self._proj is not None)
-            flat = torch.empty(plan.struct.bytes, dtype=torch.uint8, device=dev)
-            counts_h.fill(-1)
-            rc = L.pemp_step_fully_cap(plan.ref, self._detect_src(sm), _lib.ptr(masks), _lib.ptr(feats), _lib.ptr(tags),
-                                       flat.data_ptr(), counts_h.ctypes.data, st)
-            if rc == _lib.ERR_UNSUPPORTED and mi is not None:
-                mpn._cap_ok = False     # the forward's conditions refused this model: the exact forward from now on
-                mi = None
-            else:
-                _lib.check(rc)
-            yield None                                       # (construct_graph_start returns here)
-            counts_l = self._wait_counts(counts_h, dev)
-            out = plan.outputs(flat, counts_l, cap, tags, mpn if mi is not None else None, mi)
-            if out is not None:
-                self._update_hint(gkey, counts_l)
-                if proj_tags is not None:   # sampled at the detections (pemp_gather_projected_tags)
-                    out = out[:14] + (self._gather_proj_tags(L, st, proj_tags, J, H, W, out[7], out[12],
-                                                             out[0].shape[0], dev),)
-                return out
-            # a capacity was exceeded: the exact path below on the step's detections
-            ws = plan.det_ws
-            det, dsc, n_det = plan.detections(flat)
-            hint = None
         else:
-            ws = self._ws_detect.get(L.pemp_detect_workspace_size(B, J, H, W, topk), dev)
-            det = torch.empty(B, cap, 3, dtype=torch.int64, device=dev)
-            dsc = torch.empty(B, cap, dtype=torch.float32, device=dev)
-            n_det = torch.empty(B, dtype=torch.int32, device=dev)
-        if hint is not None:
-            n_cap, e_cap = hint
-            bufs = (torch.empty(n_cap, C, dtype=torch.float32, device=dev),
-                    torch.empty(n_cap, 3, dtype=torch.int64, device=dev),
-                    torch.empty(n_cap, dtype=torch.float32, device=dev),
-                    torch.empty(n_cap, dtype=torch.int64, device=dev),
-                    torch.empty(n_cap, F, dtype=torch.float32, device=dev) if tags is not None else None,
-                    torch.empty(2 * e_cap, dtype=torch.int64, device=dev),
-                    torch.empty(e_cap, A, dtype=torch.float32, device=dev),
-                    # node offsets (MPN fast path), then the batch's (N, E, overflow) for the capacity-mode MPN
-                    torch.empty(B + 4, dtype=torch.int64, device=dev))
-            build_args = (_lib.ptr(n_det), B, _lib.ptr(det), _lib.ptr(dsc), cap, _lib.ptr(feats), C, _lib.ptr(tags), F,
-                          J, H, W, n_cap, e_cap, norm, mode | (_lib.BUILD_WRITE_COUNTS if _BUILD_COUNTS else 0),
-                          *[_lib.ptr(t) for t in bufs], st)
-            mpn = NaiveGraphConstructor._bound_mpn
-            if mpn is not None and not projected and J == getattr(mpn, "num_types", None):
-                pending_mpn = mpn
-                launch_mpn = mpn._prepare_cap(bufs[0], bufs[6], bufs[1], n_cap, e_cap, n_det, cap, bufs[7], B,
-                                              counts_in_off=_BUILD_COUNTS)
-        if step:
-            pass                                             # (queued, and the counts read, above)
-        elif hint is not None:
-            # capacity mode: the graph build (and the bound MPN) queued before the counts are read, so the GPU
-            # builds the graph while the host waits for them (pemp_fully_graph_build_cap)
-            self._detect_launch(L, st, sm, masks, B, J, H, W, use_thr, topk, thr, ws, det, dsc, n_det, cap, counts_h)
-            _lib.check(L.pemp_fully_graph_build_cap(*build_args))
-            if launch_mpn is not None:
-                pending = launch_mpn()
-            yield None                                       # (construct_graph_start returns here)
-            counts_l = self._wait_counts(counts_h, dev)
-            built = bufs
-        else:
-            self._detect_launch(L, st, sm, masks, B, J, H, W, use_thr, topk, thr, ws, det, dsc, n_det, cap, counts_h)
-            yield None
-            counts_l = self._wait_counts(counts_h, dev)      # the one host read-back of the batch
+            _lib.check(rc)
+        yield None                                       # (construct_graph_start returns here)
+        counts_l = self._wait_counts(c.counts_h, c.dev)
+        built = plan.outputs(flat, counts_l, mpn if mi is not None else None)
+        if built is None:     # a capacity was exceeded: the exact build on the step's detections
+            return self._exact_build(c, plan.detections(flat), cap, counts_l)
+        self._update_hint(c.gkey, counts_l)
+        return self._finish(c, *built, True)
+
+    def _cap_stage(self, c, cap, hint):
+        """A repeated fully-graph batch shape with ProjectedMaps features: the detection, then the capacity build queued
+        ahead of the count wait (pemp_fully_graph_build_cap), then x sampled for the counts the host has read."""
+        n_cap, e_cap = hint
+        dets = self._det_alloc(c, cap)
+        bufs = self._fully_bufs(c, n_cap, e_cap, c.B + 4)   # node offsets, then the batch's (N, E, overflow)
+        self._detect_launch(c, dets, cap)
+        self._fully_launch(c, c.L.pemp_fully_graph_build_cap, dets, cap, bufs)
+        yield None                                       # (construct_graph_start returns here)
+        counts_l = self._wait_counts(c.counts_h, c.dev)
+        fit = _fits(counts_l, cap, n_cap, e_cap)
+        if fit is None:
+            return self._exact_build(c, dets, cap, counts_l)
+        self._update_hint(c.gkey, counts_l)
+        N, E = fit      # the outputs are leading (contiguous) slices of the capacity buffers
+        nodes = tuple(None if t is None else t[:N] for t in bufs[:5])
+        edge_index = bufs[5].view(-1)[:2 * E].view(2, E)
+        _tag_fully(edge_index, bufs[7], counts_l, nodes[1])
+        return self._finish(c, nodes, bufs[6][:E], edge_index, True)
+
+    def _exact_stage(self, c, cap):
+        """No capacities for this batch: the detection alone is queued, the graph is built for the exact counts."""
+        dets = self._det_alloc(c, cap)
+        self._detect_launch(c, dets, cap)
+        yield None                                       # (construct_graph_start returns here)
+        return self._exact_build(c, dets, cap, self._wait_counts(c.counts_h, c.dev))   # the one host read-back
+
+    def _exact_build(self, c, dets, cap, counts_l):
+        """The 15-tuple from the detections dets (made under capacity cap) and the counts the host has read."""
         mx = max(counts_l) if counts_l else 0
-        cap_used = cap                                      # the detections the capacity build read
-        if mx > cap:
+        if mx > cap:    # more detections than were kept: the emit stage again, into larger buffers
             cap = mx
             with NaiveGraphConstructor._mu:
                 NaiveGraphConstructor._cap = max(NaiveGraphConstructor._cap, cap)
-            det = torch.empty(B, cap, 3, dtype=torch.int64, device=dev)
-            dsc = torch.empty(B, cap, dtype=torch.float32, device=dev)
-            _lib.check(self._detect(L)(self._detect_src(sm), _lib.ptr(masks), B, J, H, W, self.pool_kernel_size, thr,
-                                       int(use_thr), topk, 2, _lib.ptr(ws), ws.numel(), _lib.ptr(det), _lib.ptr(dsc),
-                                       _lib.ptr(n_det), cap, None, st))
+            dets = self._det_alloc(c, cap, dets)
+            self._detect_launch(c, dets, cap, emit_only=True)
         N = sum(counts_l)
-        E_fully = sum(c * (c - 1) for c in counts_l if c > 1)
-        if fully:
-            self._update_hint(gkey, counts_l)
-        if built is not None and mx <= cap_used and N <= built[0].shape[0] and E_fully <= built[6].shape[0]:
-            # the capacity build fit: the outputs are leading (contiguous) slices of its buffers
-            x, joint_det, joint_scores, batch_index = built[0][:N], built[1][:N], built[2][:N], built[3][:N]
-            joint_tags = built[4][:N] if tags is not None else None
-            edge_index = built[5][:2 * E_fully].view(2, E_fully)
-            edge_attr = built[6][:E_fully]
-            if projected:
-                self._gather_projected(L, st, pmaps, pconv, H, W, joint_det, batch_index, x)
-            if tags is not None:
-                joint_tags = joint_tags.view((N,) + tuple(tags.shape[4:])) if tags.dim() > 4 else joint_tags.view(N)
-            if proj_tags is not None:
-                joint_tags = self._gather_proj_tags(L, st, proj_tags, J, H, W, joint_det, batch_index, N, dev)
-            _tag_fully(edge_index, built[7], counts_l, joint_det)
-            if pending is not None:
-                pending_mpn._attach_cap(pending, x, edge_attr, edge_index, joint_det, N, E_fully)
-            return (x, edge_attr, edge_index, None, None, None, None, joint_det, None, None, None, joint_scores,
-                    batch_index, None, joint_tags)
-        x = torch.empty(N, C, dtype=torch.float32, device=dev)
-        joint_det = torch.empty(N, 3, dtype=torch.int64, device=dev)
-        joint_scores = torch.empty(N, dtype=torch.float32, device=dev)
-        batch_index = torch.empty(N, dtype=torch.int64, device=dev)
-        joint_tags = torch.empty(N, F, dtype=torch.float32, device=dev) if tags is not None else None
-
-        if fully:
-            # one launch: offsets + nodes + edge_index + edge_attr (pemp_fully_graph_build)
-            E = sum(c * (c - 1) for c in counts_l if c > 1)
-            edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
-            edge_attr = torch.empty(E, A, dtype=torch.float32, device=dev)
-            node_off = torch.empty(B + 1, dtype=torch.int64, device=dev)
-            _lib.check(L.pemp_fully_graph_build(
-                _lib.ptr(n_det), B, _lib.ptr(det), _lib.ptr(dsc), cap, _lib.ptr(feats), C, _lib.ptr(tags), F, J, H, W,
-                N, E, norm, mode, _lib.ptr(x), _lib.ptr(joint_det), _lib.ptr(joint_scores), _lib.ptr(batch_index),
-                _lib.ptr(joint_tags), _lib.ptr(edge_index), _lib.ptr(edge_attr), _lib.ptr(node_off), st))
+        if c.fully:     # one launch: offsets + nodes + edge_index + edge_attr (pemp_fully_graph_build)
+            self._update_hint(c.gkey, counts_l)
+            bufs = self._fully_bufs(c, N, _fully_edges(counts_l), c.B + 1)
+            self._fully_launch(c, c.L.pemp_fully_graph_build, dets, cap, bufs)
+            nodes, edge_index, edge_attr, node_off = bufs[:5], bufs[5], bufs[6], bufs[7]
             if N > 0:
-                _tag_fully(edge_index, node_off, counts_l, joint_det)
+                _tag_fully(edge_index, node_off, counts_l, nodes[1])
         else:
-            node_off_h = np.zeros(B + 1, np.int64)
-            node_off_h[1:] = np.cumsum(np.asarray(counts_l, np.int64))
-            # batch offsets are recomputed on the device from n_det (no host->device upload)
-            offs = torch.empty(2, B + 1, dtype=torch.int64, device=dev)
-            node_off, fully_off = offs[0], offs[1]
-            _lib.check(L.pemp_graph_offsets(_lib.ptr(n_det), B, _lib.ptr(node_off),
-                                            _lib.ptr(fully_off) if self.mpn_graph_type == "fully" else None, st))
-            _lib.check(L.pemp_pack_nodes(_lib.ptr(feats), C, _lib.ptr(tags), F, B, J, H, W, _lib.ptr(det),
-                                         _lib.ptr(dsc), cap, _lib.ptr(node_off), N, _lib.ptr(x), _lib.ptr(joint_det),
-                                         _lib.ptr(joint_scores), _lib.ptr(batch_index), _lib.ptr(joint_tags), st))
-            if proj_tags is not None:   # before the edge features, which may read them
-                joint_tags = self._gather_proj_tags(L, st, proj_tags, J, H, W, joint_det, batch_index, N, dev)
-            if self.mpn_graph_type in ("knn", "feature_knn"):   # edge features written by the knn emit itself
-                if self.mpn_graph_type == "feature_knn" and projected:   # the graph ranks by x: sample it first
-                    self._gather_projected(L, st, pmaps, pconv, H, W, joint_det, batch_index, x)
-                    projected = False
-                edge_index, edge_attr = self._knn_edges(L, st, joint_det, joint_tags, F, joint_scores, node_off,
-                                                        node_off_h, B, J, A, norm, mode, dev,
-                                                        x if self.mpn_graph_type == "feature_knn" else None)
-                _tag_sym(edge_index)
-            else:
-                edge_index = self._edges(L, st, joint_det, joint_scores, node_off, fully_off, node_off_h, B, dev)
-                if self.mpn_graph_type == "score_based":
-                    _tag_sym(edge_index)
-                E = edge_index.shape[1]
-                edge_attr = torch.empty(E, A, dtype=torch.float32, device=dev)
-                _lib.check(L.pemp_edge_features(_lib.ptr(joint_det), _lib.ptr(joint_tags), F, _lib.ptr(joint_scores),
-                                                _lib.ptr(edge_index), E, J, norm, mode,
-                                                _lib.ptr(edge_attr), st))
-        if projected:
-            self._gather_projected(L, st, pmaps, pconv, H, W, joint_det, batch_index, x)
-        if tags is not None:
-            joint_tags = joint_tags.view((N,) + tuple(tags.shape[4:])) if tags.dim() > 4 else joint_tags.view(N)
-        if proj_tags is not None and fully:
-            joint_tags = self._gather_proj_tags(L, st, proj_tags, J, H, W, joint_det, batch_index, N, dev)
-        out = (x, edge_attr, edge_index, None, None, None, None, joint_det, None, None, None, joint_scores,
-               batch_index, None, joint_tags)
+            nodes, edge_index, edge_attr, node_off = self._build_generic(c, dets, cap, counts_l, N)
+        out = self._finish(c, nodes, edge_attr, edge_index, c.fully)
         if self._labels is not None:
-            out = self._label_outputs(L, st, out, node_off, counts_l, B, H, W, dev)
+            out = self._label_outputs(c, out, node_off, counts_l)
         return out
+
+    @staticmethod
+    def _node_bufs(c, n):
+        """x, joint_det, joint_scores, batch_index and (dense tagmaps only) joint_tags for n nodes."""
+        f32, i64, dev = torch.float32, torch.int64, c.dev
+        return (torch.empty(n, c.C, dtype=f32, device=dev), torch.empty(n, 3, dtype=i64, device=dev),
+                torch.empty(n, dtype=f32, device=dev), torch.empty(n, dtype=i64, device=dev),
+                torch.empty(n, c.F, dtype=f32, device=dev) if c.tags is not None else None)
+
+    def _fully_bufs(self, c, n, e, n_off):
+        """The fused fully-graph build's outputs: the node arrays, edge_index, edge_attr, node_off [n_off]."""
+        return self._node_bufs(c, n) + (torch.empty(2, e, dtype=torch.int64, device=c.dev),
+                                        torch.empty(e, c.A, dtype=torch.float32, device=c.dev),
+                                        torch.empty(n_off, dtype=torch.int64, device=c.dev))
+
+    @staticmethod
+    def _fully_launch(c, build, dets, cap, bufs):
+        """pemp_fully_graph_build / _cap into bufs (_fully_bufs: their sizes are the exact counts / the capacities)."""
+        _, det, dsc, n_det = dets
+        _lib.check(build(_lib.ptr(n_det), c.B, _lib.ptr(det), _lib.ptr(dsc), cap, _lib.ptr(c.feats), c.C,
+                         _lib.ptr(c.tags), c.F, c.J, c.H, c.W, bufs[0].shape[0], bufs[6].shape[0], c.norm, c.mode,
+                         *[_lib.ptr(t) for t in bufs], c.st))
+
+    def _finish(self, c, nodes, edge_attr, edge_index, late_tags):
+        """The inference 15-tuple of a built graph (ConstructGraph.py:232-249, the label slots None): x sampled where
+        the features are projected maps and the build did not need it, the tags in the reference's shape (projected
+        ones sampled now when late_tags)."""
+        x, joint_det, joint_scores, batch_index, joint_tags = nodes
+        N = x.shape[0]
+        if c.pmaps is not None and self.mpn_graph_type != "feature_knn":
+            self._gather_projected(c, joint_det, batch_index, x)
+        if c.tags is not None:   # [N, F] as the reference's tagmaps[b, type, y, x] rows: [N, *tags.shape[4:]] or [N]
+            joint_tags = joint_tags.view((N,) + tuple(c.tags.shape[4:]) if c.tags.dim() > 4 else (N,))
+        if c.ptags is not None and late_tags:
+            joint_tags = self._gather_proj_tags(c, joint_det, batch_index, N)
+        return (x, edge_attr, edge_index, None, None, None, None, joint_det, None, None, None, joint_scores,
+                batch_index, None, joint_tags)
+
+    def _build_generic(self, c, dets, cap, counts_l, N):
+        """Offsets, node pack, then the graph type's edges and their features, a launch each (knn, feature_knn,
+        score_based; fully where the fused build does not apply): (node buffers, edge_index, edge_attr, node_off)."""
+        L, st, B, gtype = c.L, c.st, c.B, self.mpn_graph_type
+        _, det, dsc, n_det = dets
+        x, joint_det, joint_scores, batch_index, joint_tags = nodes = self._node_bufs(c, N)
+        node_off_h = np.zeros(B + 1, np.int64)
+        node_off_h[1:] = np.cumsum(np.asarray(counts_l, np.int64))
+        # batch offsets are recomputed on the device from n_det (no host->device upload)
+        offs = torch.empty(2, B + 1, dtype=torch.int64, device=c.dev)
+        node_off, fully_off = offs[0], offs[1]
+        _lib.check(L.pemp_graph_offsets(_lib.ptr(n_det), B, _lib.ptr(node_off),
+                                        _lib.ptr(fully_off) if gtype == "fully" else None, st))
+        _lib.check(L.pemp_pack_nodes(_lib.ptr(c.feats), c.C, _lib.ptr(c.tags), c.F, B, c.J, c.H, c.W, _lib.ptr(det),
+                                     _lib.ptr(dsc), cap, _lib.ptr(node_off), N, _lib.ptr(x), _lib.ptr(joint_det),
+                                     _lib.ptr(joint_scores), _lib.ptr(batch_index), _lib.ptr(joint_tags), st))
+        if c.ptags is not None:   # before the edge features, which may read them
+            nodes = nodes[:4] + (self._gather_proj_tags(c, joint_det, batch_index, N),)
+        if gtype in ("knn", "feature_knn"):   # edge features written by the knn emit itself
+            by_x = gtype == "feature_knn"
+            if by_x and c.pmaps is not None:   # the graph ranks by x: sample it first
+                self._gather_projected(c, joint_det, batch_index, x)
+            edge_index, edge_attr = self._knn_edges(c, joint_det, nodes[4], joint_scores, node_off, node_off_h,
+                                                    x if by_x else None)
+        else:
+            edge_index = self._edges(c, joint_scores, node_off, fully_off, node_off_h)
+            E = edge_index.shape[1]
+            edge_attr = torch.empty(E, c.A, dtype=torch.float32, device=c.dev)
+            _lib.check(L.pemp_edge_features(_lib.ptr(joint_det), _lib.ptr(nodes[4]), c.F, _lib.ptr(joint_scores),
+                                            _lib.ptr(edge_index), E, c.J, c.norm, c.mode, _lib.ptr(edge_attr), st))
+        if gtype != "fully":   # knn, feature_knn, score_based: to_undirected's output
+            _tag_sym(edge_index)
+        return nodes, edge_index, edge_attr, node_off
 
     @staticmethod
     def _update_hint(gkey, counts_l):
         """Capacities for the next batch of this shape: 25 % headroom over this one (grow-only)."""
-        N = sum(counts_l)
-        E = sum(c * (c - 1) for c in counts_l if c > 1)
+        N, E = sum(counts_l), _fully_edges(counts_l)
         n_hint = (N + N // 4 + 16, E + E // 4 + 256)
         with NaiveGraphConstructor._mu:
             old = NaiveGraphConstructor._graph_hint.get(gkey)
             NaiveGraphConstructor._graph_hint[gkey] = n_hint if old is None else (
                 max(old[0], n_hint[0]), max(old[1], n_hint[1]))
 
-    def _detect_launch(self, L, st, sm, masks, B, J, H, W, use_thr, topk, thr, ws, det, dsc, n_det, cap, counts_h):
-        counts_h.fill(-1)
-        _lib.check(self._detect(L)(self._detect_src(sm), _lib.ptr(masks), B, J, H, W, self.pool_kernel_size, thr,
-                                   int(use_thr), topk, 3, _lib.ptr(ws), ws.numel(), _lib.ptr(det), _lib.ptr(dsc),
-                                   _lib.ptr(n_det), cap, counts_h.ctypes.data, st))
+    def _det_alloc(self, c, cap, old=None):
+        """(workspace, det_xyt [B, cap, 3], det_scores [B, cap], n_det [B]); old: its workspace and n_det kept."""
+        ws = old[0] if old else self._ws_detect.get(c.L.pemp_detect_workspace_size(c.B, c.J, c.H, c.W, c.topk), c.dev)
+        return (ws, torch.empty(c.B, cap, 3, dtype=torch.int64, device=c.dev),
+                torch.empty(c.B, cap, dtype=torch.float32, device=c.dev),
+                old[3] if old else torch.empty(c.B, dtype=torch.int32, device=c.dev))
+
+    @staticmethod
+    def _detect_launch(c, dets, cap, emit_only=False):
+        """pemp_detect; emit_only: its emit stage again (the counts are on the host already)."""
+        ws, det, dsc, n_det = dets
+        if not emit_only:
+            c.counts_h.fill(-1)
+        _lib.check(c.detect(c.src, _lib.ptr(c.masks), c.B, c.J, c.H, c.W, c.pool, c.thr, int(c.use_thr), c.topk,
+                            2 if emit_only else 3, _lib.ptr(ws), ws.numel(), _lib.ptr(det), _lib.ptr(dsc),
+                            _lib.ptr(n_det), cap, None if emit_only else c.counts_h.ctypes.data, c.st))
 
     _plans = {}   # (device, stream, batch shape, capacities, forward) -> _StepPlan (under _mu)
 
-    def _step_plan(self, L, dev, st, B, J, H, W, use_thr, topk, thr, cap, C, F, A, mode, norm, n_cap, e_cap, mi,
-                   proj):
+    def _step_plan(self, c, cap, n_cap, e_cap, mi):
         """The pemp_step_fully_cap plan of this call's arguments (cached per device, stream and shape)."""
         fkey = None if mi is None else (id(mi[1]), mi[2].data_ptr(), mi[2].numel(), ctypes.addressof(mi[0]))
-        key = (dev.index, st, B, J, H, W, self.pool_kernel_size, use_thr, topk, thr, cap, C, F, A, mode, norm, n_cap,
-               e_cap, fkey, proj)
+        key = (c.gkey, c.st, c.pool, c.use_thr, c.topk, c.thr, cap, c.tags is not None, c.mode, c.norm, n_cap, e_cap,
+               fkey, c.proj)   # (gkey: the shape B, J, H, W, C, F, A and the device)
         with NaiveGraphConstructor._mu:
             plan = NaiveGraphConstructor._plans.get(key)
         if plan is None:
-            ws = self._ws_detect.get(L.pemp_detect_workspace_size(B, J, H, W, topk), dev)
-            plan = _StepPlan(L, B, J, H, W, self.pool_kernel_size, use_thr, topk, thr, cap, ws, C, F, A, mode, norm,
-                             n_cap, e_cap, mi, proj)
+            ws = self._ws_detect.get(c.L.pemp_detect_workspace_size(c.B, c.J, c.H, c.W, c.topk), c.dev)
+            plan = _StepPlan(c, cap, ws, n_cap, e_cap, mi)
             with NaiveGraphConstructor._mu:
                 if len(NaiveGraphConstructor._plans) >= 64:
                     NaiveGraphConstructor._plans.clear()
                 NaiveGraphConstructor._plans[key] = plan
         return plan
 
-    def _detect(self, L):
-        return L.pemp_detect_projected if self._proj is not None else L.pemp_detect
-
-    def _detect_src(self, sm):
-        return ctypes.addressof(self._proj_c) if self._proj is not None else _lib.ptr(sm)
-
-    def _gather_proj_tags(self, L, st, pt, J, H, W, joint_det, batch_index, N, dev):
+    @staticmethod
+    def _gather_proj_tags(c, joint_det, batch_index, N):
         """joint_tags [N, F] from the projected tag channels (pemp_gather_projected_tags); the reference's
         tagmaps there are [B, J, H, W, F] (torch.cat(tags_list, dim=4)), so F = 1 stays [N, 1]."""
-        F = pt.tag_dims
-        jt = torch.empty(N, F, dtype=torch.float32, device=dev)
-        c = pt.c_struct()
-        _lib.check(L.pemp_gather_projected_tags(ctypes.addressof(c), pt.tag_scale, J, H, W, _lib.ptr(joint_det),
-                                                _lib.ptr(batch_index), N, _lib.ptr(jt), st))
+        pt = c.ptags
+        jt = torch.empty(N, pt.tag_dims, dtype=torch.float32, device=c.dev)
+        maps = pt.c_struct()
+        _lib.check(c.L.pemp_gather_projected_tags(ctypes.addressof(maps), pt.tag_scale, c.J, c.H, c.W,
+                                                  _lib.ptr(joint_det), _lib.ptr(batch_index), N, _lib.ptr(jt), c.st))
         return jt
 
-    def _gather_projected(self, L, st, pmaps, pconv, H, W, joint_det, batch_index, x):
+    @staticmethod
+    def _gather_projected(c, joint_det, batch_index, x):
+        """x [N, C] sampled at the detections from the projected maps (pemp_gather_projected), through the
+        feature_gather conv at the taps where the maps carry one (pemp_gather_projected_conv)."""
+        L, pmaps, vp = c.L, c.pmaps, ctypes.c_void_p
         S = len(pmaps)
-        ptrs = (ctypes.c_void_p * S)(*[m.data_ptr() for m in pmaps])
-        hs = (ctypes.c_int32 * S)(*[m.shape[2] for m in pmaps])
-        ws = (ctypes.c_int32 * S)(*[m.shape[3] for m in pmaps])
-        vp = ctypes.c_void_p
-        if pconv is not None:   # feature_gather conv at the taps (pemp_gather_projected_conv)
-            wt, b, k, pad = pconv
-            _lib.check(L.pemp_gather_projected_conv(ctypes.cast(ptrs, vp), ctypes.cast(hs, vp), ctypes.cast(ws, vp), S,
-                                                    pmaps[0].shape[1], _lib.ptr(wt), _lib.ptr(b), x.shape[1], k, pad,
-                                                    H, W, self.features.divisor, _lib.ptr(joint_det),
-                                                    _lib.ptr(batch_index), x.shape[0], _lib.ptr(x), st))
-            return
-        _lib.check(L.pemp_gather_projected(ctypes.cast(ptrs, vp), ctypes.cast(hs, vp), ctypes.cast(ws, vp), S,
-                                           x.shape[1], H, W, self.features.divisor,
-                                           _lib.ptr(joint_det), _lib.ptr(batch_index), x.shape[0], _lib.ptr(x), st))
+        ptrs = ctypes.cast((vp * S)(*[m.data_ptr() for m in pmaps]), vp)
+        hs = ctypes.cast((ctypes.c_int32 * S)(*[m.shape[2] for m in pmaps]), vp)
+        ws = ctypes.cast((ctypes.c_int32 * S)(*[m.shape[3] for m in pmaps]), vp)
+        tail = (c.H, c.W, c.divisor, _lib.ptr(joint_det), _lib.ptr(batch_index), x.shape[0], _lib.ptr(x), c.st)
+        if c.pconv is not None:
+            wt, b, k, pad = c.pconv
+            _lib.check(L.pemp_gather_projected_conv(ptrs, hs, ws, S, pmaps[0].shape[1], _lib.ptr(wt), _lib.ptr(b),
+                                                    x.shape[1], k, pad, *tail))
+        else:
+            _lib.check(L.pemp_gather_projected(ptrs, hs, ws, S, x.shape[1], *tail))
 
-    def _edges(self, L, st, joint_det, joint_scores, node_off, fully_off, node_off_h, B, dev):
+    def _edges(self, c, joint_scores, node_off, fully_off, node_off_h):
+        L, st, B, dev = c.L, c.st, c.B, c.dev
         counts = np.diff(node_off_h)
         if self.mpn_graph_type == "fully":
-            per = counts * np.maximum(counts - 1, 0)
-        elif self.mpn_graph_type == "score_based":
-            k = _SCORE_BASED_K
-            if counts.size and counts.min() < k:   # the reference's joint_scores.topk(k) raises
-                raise RuntimeError(f"score_based graph: selected index k={k} out of range for "
-                                   f"{int(counts.min())} detections")
-            per = k * (2 * counts - k - 1)
-        else:
-            raise NotImplementedError(f"GRAPH_TYPE={self.mpn_graph_type}")
-        E = int(per.sum())
-        edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
-        if self.mpn_graph_type == "fully":
+            E = int((counts * np.maximum(counts - 1, 0)).sum())
+            edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
             _lib.check(L.pemp_fully_graph(_lib.ptr(node_off), _lib.ptr(fully_off), B, E, _lib.ptr(edge_index), st))
-        elif self.mpn_graph_type == "score_based":
-            nh = np.ascontiguousarray(node_off_h)
-            nh_p = nh.ctypes.data_as(ctypes.c_void_p)
-            ws = self._ws_knn.get(L.pemp_score_graph_workspace_size(nh_p, B, _SCORE_BASED_K), dev)
-            _lib.check(L.pemp_score_graph(_lib.ptr(joint_scores), _lib.ptr(node_off), nh_p, B, _SCORE_BASED_K, E,
-                                          _lib.ptr(ws), ws.numel(), _lib.ptr(edge_index), st))
+            return edge_index
+        if self.mpn_graph_type != "score_based":
+            raise NotImplementedError(f"GRAPH_TYPE={self.mpn_graph_type}")
+        k = _SCORE_BASED_K
+        if counts.size and counts.min() < k:   # the reference's joint_scores.topk(k) raises
+            raise RuntimeError(f"score_based graph: selected index k={k} out of range for "
+                               f"{int(counts.min())} detections")
+        E = int((k * (2 * counts - k - 1)).sum())
+        edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
+        nh = np.ascontiguousarray(node_off_h)
+        nh_p = nh.ctypes.data_as(ctypes.c_void_p)
+        ws = self._ws_knn.get(L.pemp_score_graph_workspace_size(nh_p, B, k), dev)
+        _lib.check(L.pemp_score_graph(_lib.ptr(joint_scores), _lib.ptr(node_off), nh_p, B, k, E, _lib.ptr(ws),
+                                      ws.numel(), _lib.ptr(edge_index), st))
         return edge_index
 
     _KNN_K = 50   # ConstructGraph.py:365 (knn_graph(k=50))
 
-    def _knn_edges(self, L, st, joint_det, joint_tags, F, joint_scores, node_off, node_off_h, B, J, A, norm, mode,
-                   dev, x=None):
+    def _knn_edges(self, c, joint_det, joint_tags, joint_scores, node_off, node_off_h, x=None):
         """knn_mpn_graph (ConstructGraph.py:363-368) + the edge features in one queued call
         (pemp_knn_graph_build): buffers sized by the closed-form edge bound, the total back through
         mapped memory while the emit still runs; edge_index / edge_attr are the leading contiguous
         [2, E] / [E, A] blocks of those buffers. With x: feature_knn_mpn_graph (ConstructGraph.py:370-374),
         the same graph over the node features x [N, C] (pemp_feature_knn_graph_build)."""
-        k = self._KNN_K
+        L, B, A, dev, k = c.L, c.B, c.A, c.dev, self._KNN_K
         nh = np.ascontiguousarray(node_off_h)
         nh_p = nh.ctypes.data_as(ctypes.c_void_p)
         n = np.diff(nh)
@@ -738,8 +736,8 @@ class NaiveGraphConstructor:
             word = ent[2][:1]
             word.fill(-1)
             args = (_lib.ptr(joint_det), _lib.ptr(node_off), nh_p, B, k, _lib.ptr(ws), ws.numel(), e_cap,
-                    _lib.ptr(buf), ent[1], _lib.ptr(joint_tags), F, _lib.ptr(joint_scores), J, norm, mode,
-                    _lib.ptr(ea), st)
+                    _lib.ptr(buf), ent[1], _lib.ptr(joint_tags), c.F, _lib.ptr(joint_scores), c.J, c.norm, c.mode,
+                    _lib.ptr(ea), c.st)
             if x is not None:
                 _lib.check(L.pemp_feature_knn_graph_build(_lib.ptr(x), x.shape[1], *args))
             else:

@@ -78,12 +78,9 @@ class _LogitBuf:
         self.a2 = self.a1 + (nn_ + 63) // 64 * 64
         self.buf = torch.empty(self.a2 + nn_ * J, dtype=torch.float32, device=device)
 
-    def pending(self, key):
-        """A queued result as _take_cap reads it (from_pending)."""
-        return dict(buf=self.buf, a1=self.a1, a2=self.a2, n_rec=self.n_rec, key=key)
-
     @classmethod
     def from_pending(cls, pending, J):
+        """The buffer of a queued result (the dict graph_constructor's _StepPlan.outputs builds) for _take_cap."""
         self = cls.__new__(cls)
         self.buf, self.a1, self.a2, self.n_rec, self.J = (pending["buf"], pending["a1"], pending["a2"],
                                                           pending["n_rec"], J)
@@ -245,7 +242,7 @@ class NodeClassificationMPNSimple(nn.Module):
         self._folded_key = None
         self._tensors = None
         self._ws = _lib.Workspace()
-        self._descs = {}                # counts_in_off -> (key, byref of the descriptor): _descriptor
+        self._desc_ent = None           # (key, byref of the descriptor): _descriptor
         # the edge embedding fused into the first edge pass where the library has that form: None (the default) except
         # in a forward the library profiler records, True there too, False never (two launches, the same bits);
         # pemp.h PEMP_MPN_TWO_LAUNCH_FIRST / PEMP_MPN_FUSED_FIRST_PROFILED
@@ -298,24 +295,23 @@ class NodeClassificationMPNSimple(nn.Module):
         first = 0 if f is None else _lib.MPN_FUSED_FIRST_PROFILED if f else _lib.MPN_TWO_LAUNCH_FIRST
         return first | (0 if self.paired_prelude else _lib.MPN_SEPARATE_PRELUDE)
 
-    def _descriptor(self, A, C, t_stride, counts_in_off=False):
+    def _descriptor(self, A, C, t_stride):
         """byref of the library descriptor for edge_attr width A, node width C and this node_types stride, built when
-        one of those, the precision, fuse_first_pass or paired_prelude changes (self._n_rec with it); with counts_in_off the
-        PEMP_MPN_COUNTS_IN_OFFSETS one, cached on its own. (The struct itself is the byref's ``_obj``.)"""
+        one of those, the precision, fuse_first_pass or paired_prelude changes (self._n_rec with it). (The struct
+        itself is the byref's ``_obj``.)"""
         dkey = (A, C, self.precision, t_stride, self.fuse_first_pass, self.paired_prelude)
-        ent = self._descs.get(counts_in_off)
+        ent = self._desc_ent
         if ent is None or ent[0] != dkey:
             steps, aux = self.edge_steps, self.aux_loss_steps
             self._n_rec = sum(1 for i in range(steps) if i >= steps - aux - 1)
-            flags = self._first_flag() | (_lib.MPN_COUNTS_IN_OFFSETS if counts_in_off else 0)
             desc = _lib.PempMpnDesc(self.num_types, self.num_joints, steps, aux, self.aggr_code, 64, A, C,
-                                    PRECISIONS[self.precision], t_stride, flags)
-            ent = self._descs[counts_in_off] = (dkey, ctypes.byref(desc))
+                                    PRECISIONS[self.precision], t_stride, self._first_flag())
+            ent = self._desc_ent = (dkey, ctypes.byref(desc))
         return ent[1]
 
-    # the plain descriptor of the last forward (tests and tools read the edge order back with it)
-    _desc_ref = property(lambda self: self._descs[False][1])
-    _desc = property(lambda self: self._descs[False][1]._obj)
+    # the descriptor of the last forward (tests and tools read the edge order back with it)
+    _desc_ref = property(lambda self: self._desc_ent[1])
+    _desc = property(lambda self: self._desc_ent[1]._obj)
 
     def _forward_blocks(self, x, edge_attr, edge_index, node_types, kwargs):
         """A call over the library's size limit: the nodes are cut into contiguous blocks that no edge crosses
@@ -419,53 +415,16 @@ class NodeClassificationMPNSimple(nn.Module):
 
 
     # ---- capacity mode (graph_constructor.bind_mpn): the forward queued before the detection counts are known ----
-    def _prepare_cap(self, x, edge_attr, joint_det, n_cap, e_cap, n_det, det_cap, node_off, B, counts_in_off=False):
-        """Queue pemp_mpn_forward_fully_cap on the capacity buffers of pemp_fully_graph_build_cap (x [n_cap, C],
-        edge_attr [e_cap, A], joint_det [n_cap, 3], node_off [B + 1]) with the detection's device counts n_det, in
-        two halves: the host preparation (weights, descriptor, workspace, logit buffer) now, and the returned
-        launch() that queues the call and returns the pending result (logit buffer + the key it was computed
-        under), or None when the library refuses. None instead of a launch when this model / batch takes the exact
-        forward (training, type summaries, a detection capacity past the closed-form limit, over-size capacities).
-        The graph constructor prepares before its first launch and calls launch() right after the graph build's,
-        so nothing but the call itself separates the two on the GPU."""
-        if self.training or self.node_summary != "not" or _FULLY_OFF or x.device.type != "cuda":
-            return None
-        if e_cap > self._edge_limit or self.num_types * n_cap > self._node_rows_limit:
-            return None
-        L = _lib.lib()
-        dev = x.device
-        node_types = joint_det[:, 2]
-        fw = self._weights(dev)
-        A = edge_attr.shape[1]
-        desc = self._descriptor(A, x.shape[1], 3)
-        if counts_in_off:   # node_off [B + 4]: the build wrote the batch's (N, E, overflow) after the offsets
-            desc = self._descriptor(A, x.shape[1], 3, True)
-        ws = self._ws.get(L.pemp_mpn_workspace_size(desc, n_cap, e_cap), dev)
-        lg = _LogitBuf(self._n_rec, n_cap, e_cap, self.num_joints, dev)
-        bp = lg.buf.data_ptr()
-        args = (desc, fw.struct_ref, x.data_ptr(), edge_attr.data_ptr(), node_types.data_ptr(), n_cap, e_cap,
-                n_det.data_ptr(), det_cap, node_off.data_ptr(), B, bp, bp + 4 * lg.a1, bp + 4 * lg.a2, ws.data_ptr(),
-                ws.numel(), _lib.stream(dev))
-        result = lg.pending((dev, self.precision, self._folded_key))
-
-        def launch():
-            rc = L.pemp_mpn_forward_fully_cap(*args)
-            if rc == _lib.ERR_UNSUPPORTED:
-                return None           # the exact forward runs instead
-            _lib.check(rc)
-            return result
-        return launch
-
     def _cap_info(self, C, A, n_cap, e_cap, dev):
-        """The forward's part of a pemp_step_fully_cap plan (graph_constructor's batch-step entry): (descriptor with
-        PEMP_MPN_COUNTS_IN_OFFSETS, folded weights, workspace, key of the weights it was planned under), or None when
-        this model / capacity takes the exact forward (the conditions of _prepare_cap)."""
+        """The forward's part of a pemp_step_fully_cap plan (graph_constructor's batch-step entry): (descriptor, folded
+        weights, workspace, key of the weights it was planned under), or None when this model / capacity takes the
+        exact forward (training, type summaries, over-size capacities)."""
         if self.training or self.node_summary != "not" or _FULLY_OFF or dev.type != "cuda":
             return None
         if e_cap > self._edge_limit or self.num_types * n_cap > self._node_rows_limit:
             return None
         fw = self._weights(dev)
-        desc = self._descriptor(A, C, 3, True)
+        desc = self._descriptor(A, C, 3)
         ws = self._ws.get(_lib.lib().pemp_mpn_workspace_size(desc, n_cap, e_cap), dev)
         return desc._obj, fw, ws, (dev, self.precision, self._folded_key)
 

@@ -357,8 +357,8 @@ def test_capacity_graphs_single_key_and_debug_sync(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = {}
     for dbg in ("0", "1"):
-        # (the script counts the forward's calls through its Python binding: the three-call capacity path)
-        env = dict(os.environ, PEMP_DEBUG_SYNC=dbg, PEMP_GRAPHS="1", PEMP_STEP_ENTRY="0", PYTHONPATH=root)
+        # (the script repeats the batch-step call, whose forward is the capacity forward, through its Python binding)
+        env = dict(os.environ, PEMP_DEBUG_SYNC=dbg, PEMP_GRAPHS="1", PYTHONPATH=root)
         r = subprocess.run([sys.executable, str(script)], env=env, cwd=root, capture_output=True, text=True,
                            timeout=240)
         assert r.returncode == 0, r.stderr[-3000:]
@@ -398,7 +398,7 @@ def step():
     return [float(t.double().sum()) for t in got[0] + got[1] + got[2]]
 step()                              # sets the capacities (exact build)
 L = _lib.lib()
-real = L.pemp_mpn_forward_fully_cap
+real = L.pemp_step_fully_cap
 calls = []
 def once(*args):                    # the same argument set four times in a row: direct, capture, replay, replay
     s0 = stats()
@@ -409,9 +409,9 @@ def once(*args):                    # the same argument set four times in a row:
         torch.cuda.synchronize()
         calls.append([b - a for a, b in zip(s0, stats())])
     return 0
-L.pemp_mpn_forward_fully_cap = once
+L.pemp_step_fully_cap = once
 sums = [step()]
-L.pemp_mpn_forward_fully_cap = real
+L.pemp_step_fully_cap = real
 print(json.dumps({"per_call": calls, "sums": sums + [step()]}))
 """
 

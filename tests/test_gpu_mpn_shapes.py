@@ -146,8 +146,6 @@ def test_unfused_model_leaves_the_capacity_path(case, monkeypatch):
     published model stays on the capacity path and is served from the queued result."""
     from pemp_amd import graph_constructor as gcm
     from pemp_amd.mpn import model as mm
-    monkeypatch.setattr(gcm, "_BUILD_COUNTS", True)
-    monkeypatch.setattr(gcm, "_STEP_ENTRY", True)
     B, H, W = 2, 96, 96
     gcm.NaiveGraphConstructor._graph_hint.clear()             # capacities from earlier tests' batches of this shape
     gcm.NaiveGraphConstructor._cap = 512

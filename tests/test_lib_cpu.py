@@ -89,7 +89,7 @@ def test_step_layout_is_host_arithmetic():
     without overlap; the logit arrays laid out as mpn/model.py's forward lays them (64-element boundaries)."""
     import ctypes
     L = _lib.load_cdll()
-    desc = _lib.PempMpnDesc(17, 17, 3, 1, 3, 64, 19, 128, 2, 3, _lib.MPN_COUNTS_IN_OFFSETS)
+    desc = _lib.PempMpnDesc(17, 17, 3, 1, 3, 64, 19, 128, 2, 3, 0)
     p = _lib.PempStepPlan(B=8, J=17, H=640, W=640, pool_kernel=5, use_threshold=1, topk=5, det_cap=512, threshold=0.1,
                           C=128, F=1, A=19, mode=0, norm_factor=640.0, n_cap=1546, e_cap=232_846)
     p.desc = ctypes.pointer(desc)

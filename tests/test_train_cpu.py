@@ -1,4 +1,4 @@
-"""CPU-side checks of the training mode: the three segment entry points of libpemp.so (exported, ABI 23, argument
+"""CPU-side checks of the training mode: the three segment entry points of libpemp.so (exported, ABI 24, argument
 errors reported before any HIP call), the segment plan on CPU tensors, and the plain-torch restatement
 (tests/train_oracle.py) in fp64 against the reference's own training step (tests/golden/train_*.npz)."""
 import numpy as np
@@ -15,7 +15,7 @@ def test_exports_and_abi():
     L = _lib.load_cdll()
     for name in ("pemp_seg_aggr_fwd", "pemp_seg_aggr_bwd", "pemp_seg_rows_sum"):
         assert hasattr(L, name) and name in _lib.SIGNATURES
-    assert L.pemp_abi_version() == 23 == _lib.ABI_VERSION
+    assert L.pemp_abi_version() == 24 == _lib.ABI_VERSION
 
 
 def test_argument_errors_need_no_gpu():

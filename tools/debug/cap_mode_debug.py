@@ -12,12 +12,12 @@ model = pemp_amd.get_mpn_model(pcfg.published_mpn_config(J, 3, "attn"))
 model.load_state_dict(syn.closed_form_state_dict(model, 1.25, 1.0, 1.0))
 model = model.eval().to(DEV)
 feats = torch.from_numpy(syn.closed_form((B, 128, H, W), 0.25)).to(DEV)
-orig_fc, orig_take = mm.NodeClassificationMPNSimple._prepare_cap, mm.NodeClassificationMPNSimple._take_cap
+orig_fc, orig_take = mm.NodeClassificationMPNSimple._cap_info, mm.NodeClassificationMPNSimple._take_cap
 
 
 def fc(self, *a, **kw):
     r = orig_fc(self, *a, **kw)
-    print("  _prepare_cap ->", None if r is None else "launch", "n_cap/e_cap", a[3], a[4], flush=True)
+    print("  _cap_info ->", None if r is None else "forward planned", "n_cap/e_cap", a[2], a[3], flush=True)
     return r
 
 
@@ -28,7 +28,7 @@ def take(self, x, ea, ei, nt):
     return r
 
 
-mm.NodeClassificationMPNSimple._prepare_cap = fc
+mm.NodeClassificationMPNSimple._cap_info = fc
 mm.NodeClassificationMPNSimple._take_cap = take
 pemp_amd.bind_mpn(model)
 for seed, persons in ((1, 3), (2, 2), (3, 3)):

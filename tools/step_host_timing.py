@@ -41,7 +41,7 @@ def timed_wait(counts, d):
 gcm.NaiveGraphConstructor._wait_counts = staticmethod(timed_wait)
 
 L = bench._lib.lib()
-for fn in ("pemp_detect", "pemp_fully_graph_build_cap", "pemp_mpn_forward_fully_cap"):
+for fn in ("pemp_detect", "pemp_fully_graph_build_cap", "pemp_step_fully_cap"):
     acc[fn] = 0.0
 
     def wrap(f, name):
