@@ -1,7 +1,7 @@
 """Generate ``tests/golden/*.npz`` by running the REFERENCE's own hot-path code on CPU.
 
 TEST INFRASTRUCTURE, container-only (needs ``/root/reference``). Run:
-    PYTHONDONTWRITEBYTECODE=1 python -B oracle/gen_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python -B oracle/gen_golden.py [case names: only these are written]
 The reference's ``NaiveGraphConstructor.construct_graph`` (ConstructGraph.py:46-249) and
 ``NodeClassificationMPNSimple.forward`` (NodeClassificationMPNSimple.py:62-97) are executed from
 ``/root/reference`` under ``oracle/ref_shims.py``. Each fixture stores the inputs that are not
@@ -51,6 +51,10 @@ def gc_config(meta):
     g.DETECT_THRESHOLD = meta["thr"]
     if "features" in meta:
         g.EDGE_FEATURES_TO_USE = list(meta["features"])
+    if "hybrid_k" in meta:
+        g.HYBRID_K = meta["hybrid_k"]
+    if "norm" in meta:
+        g.NORM_NODE_DISTANCE = bool(meta["norm"])
     return g
 
 
@@ -170,6 +174,29 @@ GC_CASES = {
                             graph="score_based", pool=5, thr=0.1, mask_crowds=False), False),
     "gc_score_based_nothr": (dict(seed=9, B=1, J=17, H=64, W=80, C=128, F=1, persons=2, variant="noisy",
                                   graph="score_based", pool=3, thr=2.0, mask_crowds=False), False),
+    # the edge-feature modes without tags (ConstructGraph.py:326-335); the angle cases keep edge_attr in full and
+    # flag its theta column, which the tests compare within 2 ulp (acos differs between libraries at the last ulp)
+    "gc_conn_only_j14": (dict(seed=20, B=2, J=14, H=80, W=96, C=16, F=1, persons=2, variant="clean",
+                              graph="fully", pool=5, thr=0.1, mask_crowds=False, features=["connection_type"]), False),
+    "gc_nothing": (dict(seed=21, B=2, J=17, H=96, W=80, C=16, F=1, persons=2, variant="clean",
+                        graph="fully", pool=5, thr=0.1, mask_crowds=False, features=["nothing"]), False),
+    "gc_position": (dict(seed=22, B=2, J=17, H=96, W=80, C=16, F=1, persons=2, variant="clean",
+                         graph="fully", pool=3, thr=0.1, mask_crowds=False, features=["position"]), False),
+    "gc_angle_fully": (dict(seed=23, B=2, J=17, H=80, W=96, C=16, F=1, persons=2, variant="clean",
+                            graph="fully", pool=5, thr=0.1, mask_crowds=False, theta_col=2,
+                            features=["position", "angle", "connection_type"]), True),
+    "gc_angle_knn": (dict(seed=24, B=1, J=17, H=96, W=96, C=16, F=1, persons=5, variant="clean",
+                          graph="knn", pool=5, thr=0.1, mask_crowds=False, theta_col=2,
+                          features=["position", "angle", "connection_type"]), True),
+    # HYBRID_K other than 5 with the threshold set, NORM_NODE_DISTANCE False (the reference's default config)
+    "gc_k1": (dict(seed=25, B=1, J=17, H=64, W=96, C=16, F=1, persons=2, variant="noisy",
+                   graph="fully", pool=3, thr=0.1, mask_crowds=False, hybrid_k=1), False),
+    "gc_k9": (dict(seed=26, B=1, J=14, H=64, W=80, C=16, F=1, persons=2, variant="noisy",
+                   graph="fully", pool=3, thr=0.1, mask_crowds=True, hybrid_k=9), False),
+    "gc_k32": (dict(seed=27, B=1, J=14, H=96, W=64, C=16, F=1, persons=1, variant="noisy",
+                    graph="fully", pool=3, thr=0.1, mask_crowds=False, hybrid_k=32), False),
+    "gc_norm_off": (dict(seed=28, B=2, J=17, H=96, W=80, C=16, F=1, persons=2, variant="clean",
+                         graph="fully", pool=5, thr=0.1, mask_crowds=False, norm=False), False),
 }
 
 MPN_CASES = {
@@ -214,8 +241,8 @@ MPN_CASES = {
 
 
 def main(only=()):
-    """Regenerate every case, or only the MPN cases named in `only` (their source graphs are rebuilt
-    in memory; graph fixtures are rewritten only when named)."""
+    """Regenerate every case, or only the cases named in `only` (every other fixture stays as it is): a named
+    graph case is rewritten alone; for a named MPN case its source graph is rebuilt in memory."""
     os.makedirs(OUT, exist_ok=True)
     cg, MPN, _ = load_reference()
     graphs = {}

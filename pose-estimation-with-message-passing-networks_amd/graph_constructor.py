@@ -137,6 +137,10 @@ class _Call:
         mode, (a, b) = ef
         if mode in _EF_TAG_MODES and tags is None and ptags is None:
             raise TypeError(f"EDGE_FEATURES_TO_USE={gc.edge_features_to_use} needs tagmaps")
+        if mode in _EF_TAG_MODES and F != {6: 1, 7: 2}.get(mode, F if F in (1, 2) else 0):
+            # (ef_tag_check of graph.hip would refuse the same, after the detection has run and without the option's name)
+            raise NotImplementedError(f"EDGE_FEATURES_TO_USE={gc.edge_features_to_use} with {F} tag dims per node: ae "
+                                      "takes 1, ae_normed 2, the other tag modes 1 or 2")
         self.feats, self.pmaps, self.pconv, self.divisor, self.tags = feats, pmaps, pconv, divisor, tags
         self.ptags, self.C, self.F, self.A, self.mode, self.counts_h = ptags, C, F, a * J + b, mode, counts_h
         self.norm = float(max(W, H)) if gc.normalize_node_distance else 1.0

@@ -27,6 +27,15 @@ def sha(t: torch.Tensor) -> str:
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
 
+def check_edge_attr_theta(ea, want, col):
+    """edge_attr of an angle fixture (meta theta_col): column col within 2 ulp of the stored one (acos is not pinned
+    at the last ulp between libraries), every other column bit for bit."""
+    ea, want = ea.detach().cpu().numpy(), np.asarray(want)
+    assert ea.shape == want.shape and ea.dtype == want.dtype == np.float32
+    np.testing.assert_array_max_ulp(ea[:, col], want[:, col], maxulp=2)
+    np.testing.assert_array_equal(np.delete(ea, col, 1).view(np.uint32), np.delete(want, col, 1).view(np.uint32))
+
+
 def gc_inputs(meta, arrays):
     B, J, H, W = meta["B"], meta["J"], meta["H"], meta["W"]
     hm = torch.from_numpy(arrays["scoremaps"])
@@ -41,6 +50,10 @@ def gc_config(meta):
     g.DETECT_THRESHOLD = meta["thr"]
     if "features" in meta:
         g.EDGE_FEATURES_TO_USE = list(meta["features"])
+    if "hybrid_k" in meta:
+        g.HYBRID_K = meta["hybrid_k"]
+    if "norm" in meta:
+        g.NORM_NODE_DISTANCE = bool(meta["norm"])
     return g
 
 
