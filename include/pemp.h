@@ -567,8 +567,8 @@ int pemp_mpn_graph_stats(uint64_t* out3);
 int pemp_edge_cus_policy(int num_cus, int64_t E, int reserve_request);
 
 /* sizeof of the ABI structs as this library was built (host only; bindings check their mirrors against it):
- * which = 0 pemp_mpn_weights, 1 pemp_mpn_desc, 2 pemp_mlp, 3 pemp_proj_maps, 4 pemp_step_plan; 0 for any other
- * value. */
+ * which = 0 pemp_mpn_weights, 1 pemp_mpn_desc, 2 pemp_mlp, 3 pemp_proj_maps, 4 pemp_step_plan, 5 pemp_loss_rec; 0 for
+ * any other value. */
 size_t pemp_abi_struct_size(int which);
 
 /* pemp_mpn_forward for an edge_index sorted by (src, dst) without duplicates and symmetric (every s -> d has
@@ -641,7 +641,7 @@ int pemp_mpn_status(const pemp_mpn_desc* desc, int64_t N, int64_t E, const void*
  * Labels: detect_nms, detect_top, detect_emit, pack_nodes, fully_graph, edge_features, score_graph,
  * mpn_prepare (the sorting prepare; the closed forms report under mpn_prepare_fully, mpn_prepare_sym and
  * mpn_prepare_knn, so the filter "mpn_prepare" catches all four), node_embed, edge_embed, node_table, edge_step, edge_step_head, node_update, heads, seg_aggr_fwd,
- * seg_aggr_bwd, seg_rows_sum, edge_mlp_fwd, edge_mlp_bwd, edge_mlp_tree. Model shapes off the published one report their fall-back kernels under labels of
+ * seg_aggr_bwd, seg_rows_sum, edge_mlp_fwd, edge_mlp_bwd, edge_mlp_tree, loss_fwd, loss_reduce, loss_bwd. Model shapes off the published one report their fall-back kernels under labels of
  * their own (the filter is a substring match, so "edge_embed" and "edge_step" still catch them): edge_embed_wide
  * (an embedding layer or edge_attr_dim over 64: weights read from global memory), edge_embed_generic (the LDS
  * embedding for a shape off the fixed A <= 32 -> 32 -> 64 -> 64 -> 64 layout), edge_step_head_generic (a recorded
@@ -772,6 +772,75 @@ int pemp_edge_mlp_bwd(int64_t N, int64_t E, int We, const float* g /*[E][64]*/, 
                       const float* e_new, const float* C, const float* W2, float* g1 /*out [E][64]*/,
                       float* g_ef /*out [E][We]*/, float* dC /*out [64][We]*/, float* dW2 /*out [64][64]*/,
                       float* db2 /*out [64]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The MPN training loss (csrc/loss.hip): the node, edge and class terms of ClassMPNLossFactory (Utils/loss.py:785-862)
+ * and of the edge / node / class part of ClassMultiLossFactory (:606-621, 668-689), with the graph reduction of
+ * train.py:104-112, 140-154 (mask_node_connections per node prediction), over K_e edge predictions [E], K_n node
+ * predictions [N] and K_n class predictions [N, J] given as one pointer per list entry:
+ *   node  = (1 / K_n) sum_k L_node(pn[k], node_labels, label_mask_node)
+ *   edge  = (1 / K_e) sum_k L_edge(pe[k], edge_labels, mask_k); NaN -> 0.0 with zero gradients (:844-845, :680-681)
+ *           mask_k = edge_mask[k] when edge_mask[0] != NULL (every entry then set), else
+ *           label_mask * (sel_k[src] op sel_k[dst]), sel_k = sigmoid(pn[k]) > node_threshold | node_labels == 1,
+ *           op = & (include_bordering 0) or | (1); src = edge_index[0], dst = edge_index[1] (needs K_n >= K_e)
+ *   class = (1 / K_n) sum_k mean_n(CE(pc[k][n, :], node_classes[n]) * node_labels[n])   (node_classes NULL: none;
+ *           a class outside [0, J) makes the term NaN)
+ *   total = node_weight node + edge_weight edge + class_weight class; terms absent from `terms` are 0 and get no
+ *           gradient.
+ * L of kind PEMP_LOSS_FOCAL (FocalLoss with logits, :865-891): sum(alpha (1 - pt)^gamma BCE mask) / sum(mask), BCE =
+ * binary_cross_entropy_with_logits, pt = exp(-BCE); of kind PEMP_LOSS_BCE (BCELossWtihLogits, :893-905): the plain
+ * mean over all elements of BCE mask, times pos_weight where the target is 1.
+ * Limits: K_e <= 8, K_n <= 9, J <= 32 (PEMP_ERR_UNSUPPORTED beyond). fp32 rows, contiguous; int64 edge_index [2, E]
+ * and node_classes [N]. Ids of edge_index outside [0, N) are never followed (that end counts as not selected).
+ *
+ * pemp_loss_fwd: out [PEMP_LOSS_OUT] floats: out[0..3] = node, edge, class, total; out[4] the class scale
+ *   class_weight / (K_n N); out[8 + k] the edge scales edge_weight / (K_e denominator_k) (all 0 under the NaN rule),
+ *   out[16 + k] the node scales: what pemp_loss_bwd multiplies dF/dx by. Two launches (labels loss_fwd, loss_reduce):
+ *   every block stores fp64 partial sums into a workspace slot of its own, one block adds the slots in a fixed order.
+ *   No atomics; bitwise reproducible; the summation order depends on (N, E, K_e, K_n) alone.
+ * pemp_loss_bwd: one launch (label loss_bwd): g_pe[k] [E], g_pn[k] [N], g_pc[k] [N, J] = d total / d logits times the
+ *   device scalar grad_total[0] (NULL: 1), recomputed from the logits and `out`; host arrays of K_e / K_n / K_n device
+ *   pointers, a NULL array or entry is skipped, every element of the others is written once. The node logits get
+ *   the node term's gradient only (sel_k is detached).
+ * Neither entry synchronises or allocates (both may be captured into a graph). Argument errors are reported before
+ * any launch. pemp_loss_workspace_size is host arithmetic: per edge block (one per PEMP_LOSS_CHUNK edges, at most
+ * 1024) 2 K_e doubles, per node block (K_n per 256 nodes, at most 64 K_n) 3 doubles, each array 256-byte aligned,
+ * plus 256; 0 for arguments outside the limits.
+ * ---------------------------------------------------------------------------------------- */
+#define PEMP_LOSS_MAXKE 8
+#define PEMP_LOSS_MAXKN 9
+#define PEMP_LOSS_MAXJ 32
+#define PEMP_LOSS_OUT 32
+#define PEMP_LOSS_CHUNK 2048
+enum { PEMP_LOSS_FOCAL = 0, PEMP_LOSS_BCE = 1 };
+enum { PEMP_LOSS_TERM_NODE = 1, PEMP_LOSS_TERM_EDGE = 2, PEMP_LOSS_TERM_CLASS = 4 };
+typedef struct pemp_loss_rec {
+  int64_t N, E;
+  int32_t J, K_e, K_n;
+  int32_t edge_kind, node_kind;     /* PEMP_LOSS_FOCAL / PEMP_LOSS_BCE */
+  int32_t include_bordering;        /* 0: both ends selected, 1: either (LOSS.INCLUDE_BORDERING_NODES) */
+  int32_t terms;                    /* PEMP_LOSS_TERM_* bits */
+  int32_t pad_;
+  float alpha, gamma;               /* FOCAL_ALPHA, FOCAL_GAMMA (gamma == 2 takes the multiply form) */
+  float edge_pos_weight, node_pos_weight;
+  float node_threshold;             /* MODEL.MPN.NODE_THRESHOLD */
+  float node_weight, edge_weight, class_weight;
+  const float* pe[PEMP_LOSS_MAXKE];
+  const float* pn[PEMP_LOSS_MAXKN];
+  const float* pc[PEMP_LOSS_MAXKN];
+  const int64_t* edge_index;
+  const float* edge_labels;
+  const float* label_mask;
+  const float* node_labels;
+  const float* label_mask_node;
+  const int64_t* node_classes;      /* or NULL: no class term */
+  const float* edge_mask[PEMP_LOSS_MAXKE];   /* caller-made mask_k, or all NULL */
+} pemp_loss_rec;
+size_t pemp_loss_workspace_size(int64_t N, int64_t E, int K_e, int K_n);
+int pemp_loss_fwd(const pemp_loss_rec* rec, void* workspace, size_t workspace_bytes, float* out /*[PEMP_LOSS_OUT]*/,
+                  void* stream);
+int pemp_loss_bwd(const pemp_loss_rec* rec, const float* out, const float* grad_total, float* const* g_pe,
+                  float* const* g_pn, float* const* g_pc, void* stream);
 
 #ifdef __cplusplus
 }

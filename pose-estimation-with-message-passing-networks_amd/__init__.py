@@ -28,6 +28,18 @@ def bind_mpn(model):
     _n.bind_mpn(model)
 
 
+_LOSS_NAMES = ("mpn_loss", "MPNLoss", "ClassMPNLossFactory", "mask_node_connections")
+
+
+def __getattr__(name):
+    """The training loss (loss.py): ``mpn_loss``, ``MPNLoss``, ``ClassMPNLossFactory``, ``mask_node_connections``;
+    imported on first use, like the entries above."""
+    if name in _LOSS_NAMES:
+        from . import loss as _l
+        return getattr(_l, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def ProjectedMaps(maps, size, divisor=None, gather=None):
     """Lazy image-size projection of per-scale feature maps for ``features=`` (frontend.py); ``gather``: the
     model's feature_gather Conv2d, evaluated at the detections only."""

@@ -64,6 +64,21 @@ class PempStepPlan(ctypes.Structure):
                 ("off", c_sz * STEP_NOUT), ("bytes", c_sz)]
 
 
+LOSS_MAXKE, LOSS_MAXKN, LOSS_MAXJ, LOSS_OUT, LOSS_CHUNK = 8, 9, 32, 32, 2048   # pemp.h PEMP_LOSS_*
+LOSS_FOCAL, LOSS_BCE = 0, 1
+LOSS_TERM_NODE, LOSS_TERM_EDGE, LOSS_TERM_CLASS = 1, 2, 4
+
+
+class PempLossRec(ctypes.Structure):
+    _fields_ = [("N", c_i64), ("E", c_i64), ("J", c_i32), ("K_e", c_i32), ("K_n", c_i32), ("edge_kind", c_i32),
+                ("node_kind", c_i32), ("include_bordering", c_i32), ("terms", c_i32), ("pad_", c_i32),
+                ("alpha", c_f32), ("gamma", c_f32), ("edge_pos_weight", c_f32), ("node_pos_weight", c_f32),
+                ("node_threshold", c_f32), ("node_weight", c_f32), ("edge_weight", c_f32), ("class_weight", c_f32),
+                ("pe", c_p * LOSS_MAXKE), ("pn", c_p * LOSS_MAXKN), ("pc", c_p * LOSS_MAXKN), ("edge_index", c_p),
+                ("edge_labels", c_p), ("label_mask", c_p), ("node_labels", c_p), ("label_mask_node", c_p),
+                ("node_classes", c_p), ("edge_mask", c_p * LOSS_MAXKE)]
+
+
 # name -> (restype, argtypes); every symbol of include/pemp.h
 SIGNATURES = {
     "pemp_abi_version": (c_i32, []),
@@ -155,6 +170,9 @@ SIGNATURES = {
     "pemp_edge_mlp_fwd": (c_i32, [c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "pemp_edge_mlp_bwd": (c_i32, [c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
                                   c_p]),
+    "pemp_loss_workspace_size": (c_sz, [c_i64, c_i64, c_i32, c_i32]),
+    "pemp_loss_fwd": (c_i32, [ctypes.POINTER(PempLossRec), c_p, c_sz, c_p, c_p]),
+    "pemp_loss_bwd": (c_i32, [ctypes.POINTER(PempLossRec), c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 LABEL_OVERFLOW = 1                  # pemp.h PEMP_LABEL_OVERFLOW
 LABEL_CAND_DTYPE = [("g", "<i4"), ("n", "<u4"), ("sim", "<f8")]   # pemp.h pemp_label_cand

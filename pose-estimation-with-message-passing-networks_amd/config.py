@@ -1,6 +1,6 @@
-"""Configuration surface of the hot path: the reference's ``MODEL.GC.*`` / ``MODEL.MPN.*`` keys.
+"""Configuration surface of the hot path: the reference's ``MODEL.GC.*`` / ``MODEL.MPN.*`` / ``MODEL.LOSS.*`` keys.
 
-Restates the defaults of ``src/config/default_config.py:112-165`` (yacs is not a dependency here)
+Restates the defaults of ``src/config/default_config.py:30-46, 112-165`` (yacs is not a dependency here)
 with a small attribute-dict ``CfgNode`` that reads the reference's experiment YAMLs
 (``experiments/**.yaml``) and ``KEY VALUE`` command-line overrides, as ``update_config`` /
 ``update_config_command`` do (``default_config.py:246-260``).
@@ -64,6 +64,13 @@ def _coerce(v, cur):
 def _defaults():
     return {
         "MODEL": {
+            # default_config.py:30-46; new keys allowed for LOSS_WEIGHTS, which the experiment files add (:31)
+            "LOSS": CfgNode({
+                "NAME": ["edge_loss"], "NODE_WEIGHT": 1.0, "EDGE_WEIGHT": 1.0, "CLASS_WEIGHT": 1.0, "TAG_WEIGHT": 1.0,
+                "SYNC_TAGS": False, "SYNC_GT_TAGS": False, "USE_FOCAL": True, "EDGE_WITH_LOGITS": True,
+                "NODE_USE_FOCAL": True, "FOCAL_ALPHA": 1.0, "FOCAL_GAMMA": 2.0, "NODE_BCE_POS_WEIGHT": 1.0,
+                "EDGE_BCE_POS_WEIGHT": 1.0, "INCLUDE_BORDERING_NODES": False,
+            }, new_allowed=True),
             "MPN": CfgNode({
                 "NODE_TYPE_SUMMARY": "not", "NAME": "VanillaMPN", "STEPS": 10, "EDGE_MLP": "agnostic",
                 "NODE_INPUT_DIM": 128, "AGGR_TYPE": "agnostic", "EDGE_INPUT_DIM": 19,

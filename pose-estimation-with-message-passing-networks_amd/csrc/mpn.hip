@@ -4624,6 +4624,7 @@ extern "C" size_t pemp_abi_struct_size(int which) {
     case 2: return sizeof(pemp_mlp);
     case 3: return sizeof(pemp_proj_maps);
     case 4: return sizeof(pemp_step_plan);
+    case 5: return sizeof(pemp_loss_rec);
     default: return 0;
   }
 }

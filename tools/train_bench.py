@@ -9,6 +9,12 @@ usage: python tools/train_bench.py [--iters 30] [--warmup 5] [--out profiles/tra
     kernel has to move over the time it took, as a share of the achievable HBM rate; the fused edge update
     (tr.edge_update) against the torch concatenation form of the same block.
 torch.cuda.Event timing around each call after a warm-up, medians. The operators' torch forms are the oracle's.
+
+       python tools/train_bench.py --leg loss [--out profiles/train_loss.md]
+  * the MPN loss (pemp_amd.loss.mpn_loss, csrc/loss.hip) forward + backward on the c3 graph's logits (STEPS 3,
+    AUX_LOSS_STEPS 2: 3 edge, 4 node and 4 class predictions) against tests/loss_oracle's fp32 torch form, alternating;
+    the library's launches (its event profiler) and torch's kernel count (torch.profiler);
+  * the whole step, construct labels -> forward -> loss -> backward, on a labelled batch of c3's shape with either loss.
 """
 import argparse
 import os
@@ -48,15 +54,153 @@ def samples(fn, iters, warmup):
     return ts
 
 
+def loss_leg(args):
+    import bench
+    from pemp_amd import _lib, config as pcfg, loss as pl, synthetic as syn
+    import pemp_amd
+    from tests import loss_oracle as lo
+    from tests.test_labels_cpu import label_config
+
+    dev = torch.device("cuda", 0)
+    wl = bench.WORKLOADS["c3"]
+    J = wl["J"]
+    mcfg = pcfg.published_mpn_config(J, 3, "attn")
+    mcfg.AUX_LOSS_STEPS = 2
+    model = pemp_amd.get_mpn_model(mcfg)
+    model.load_state_dict(syn.closed_form_state_dict(model, 0.5))
+    model.to(dev).train()
+    opt = dict(NODE_THRESHOLD=0.5)
+
+    # ---- the loss alone: c3's graph, the training forward's logits, synthetic labels
+    gc = pcfg.inference_gc_config(wl["graph"], 5, False)
+    hm, feats, tags = bench.make_inputs(wl, 0, dev)
+    out = bench.run_step(wl, gc, bench.make_model(wl, dev)[0], hm, feats, tags, dev)[0]
+    x, ea, ei, types = out[0].clone(), out[1].clone(), out[2].clone(), out[7][:, 2].clone()
+    N, E = x.shape[0], ei.shape[1]
+    with torch.no_grad():
+        pe, pn, pc, _ = model(x, ea, ei, node_types=types)
+    pe, pn, pc = ([t.detach().clone() for t in ts] for ts in (pe, pn, pc))
+    g = torch.Generator(device=dev).manual_seed(9)
+    persons = torch.randint(0, 9, (N,), generator=g, device=dev)
+    node_labels = (torch.rand(N, generator=g, device=dev) < 0.6).float()
+    on = node_labels == 1
+    edge_labels = (on[ei[0]] & on[ei[1]] & (persons[ei[0]] == persons[ei[1]])).float()
+    label_mask = (torch.rand(E, generator=g, device=dev) < 0.9).float()
+    mask_node = (torch.rand(N, generator=g, device=dev) < 0.9).float()
+    classes = torch.randint(0, J, (N,), generator=g, device=dev)
+    rest = (ei, edge_labels, label_mask, node_labels, mask_node, classes)
+
+    def leaves():
+        return ([t.detach().requires_grad_(True) for t in ts] for ts in (pe, pn, pc))
+
+    def loss_hip():
+        a, b, c = leaves()
+        pl.mpn_loss(a, b, c, *rest, opt)[0].backward()
+
+    def loss_torch():
+        a, b, c = leaves()
+        lo.mpn_loss(a, b, c, *rest, opt)[0].backward()
+
+    alone = {"hip": [], "torch": []}
+    for _ in range(3):
+        alone["hip"] += samples(loss_hip, args.iters, args.warmup)
+        alone["torch"] += samples(loss_torch, args.iters, args.warmup)
+    alone = {k: spread(v) for k, v in alone.items()}
+    _lib.prof_enable("loss_")
+    for _ in range(args.iters):
+        loss_hip()
+    torch.cuda.synchronize()
+    launches = {k: (n // args.iters, ms / n * 1e3) for k, (n, ms) in _lib.prof_report().items()}
+    _lib.prof_enable(None)
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            loss_torch()
+            torch.cuda.synchronize()
+        torch_kernels = sum(1 for ev in prof.events() if str(ev.device_type).endswith("CUDA"))
+    except Exception as exc:           # no tracer on this host: the count is left out, the timings stand
+        torch_kernels = f"not counted ({type(exc).__name__})"
+
+    # ---- the whole step on a labelled batch of c3's shape
+    hm_l, gt, fac = syn.make_labelled_heatmaps(7, wl["B"], J, wl["H"], wl["W"], 7)
+    lcfg = label_config(dict(graph="fully", method=6, use_neighbours=True, with_background=False,
+                             matching_radius=0.5, inclusion_radius=0.75))
+    hm_l, gt, fac = torch.from_numpy(hm_l).to(dev), torch.from_numpy(gt), torch.from_numpy(fac)
+    cfg = pcfg.get_config()
+    cfg.MODEL.MPN = mcfg
+    cfg.merge({"MODEL": {"LOSS": {"NAME": ["edge", "node", "class"]}, "MPN": {"NODE_THRESHOLD": 0.5}}})
+    loss_fn = pemp_amd.MPNLoss(cfg)
+    shape = {}
+
+    def whole(hip):
+        model.zero_grad(set_to_none=True)
+        o = pemp_amd.get_graph_constructor(lcfg, scoremaps=hm_l, features=feats, tagmaps=tags, joints_gt=gt,
+                                           factor_list=fac, masks=None, device=dev, testing=True, heatmaps=None,
+                                           num_joints=J).construct_graph()
+        shape["N"], shape["E"] = o[0].shape[0], o[2].shape[1]
+        preds = model(o[0], o[1], o[2], node_types=o[7][:, 2])
+        if hip:
+            total = loss_fn(o, preds)[0]
+        else:
+            total = lo.mpn_loss(preds[0], preds[1], preds[2], o[2], o[3], o[8], o[4], o[9], o[5], opt)[0]
+        total.backward()
+
+    step = {"hip": [], "torch": []}
+    for _ in range(3):
+        step["hip"] += samples(lambda: whole(True), args.iters, args.warmup)
+        step["torch"] += samples(lambda: whole(False), args.iters, args.warmup)
+    step = {k: spread(v) for k, v in step.items()}
+    load = os.getloadavg()
+    fmt = lambda t: f"{t[0]:.3f} ({t[1]:.3f} .. {t[2]:.3f})"
+    ok = alone["hip"][0] < alone["torch"][0]
+    inside = step["hip"][0] >= step["torch"][1] and step["hip"][0] <= step["torch"][2]
+    lines = ["# The MPN loss: one fused HIP pass each way against its torch form", "",
+             f"`python tools/train_bench.py --leg loss --iters {args.iters} --warmup {args.warmup}` on "
+             f"{torch.cuda.get_device_name(0)}; host load average {load[0]:.1f} / {load[1]:.1f} / {load[2]:.1f} on "
+             f"{os.cpu_count()} CPUs. torch.cuda.Event time around each call, 3 alternating rounds of {args.iters} calls "
+             f"after {args.warmup} warm-ups each, pooled: median (min .. max) in ms.", "",
+             "## The loss alone, forward + backward", "",
+             f"bench.py's c3 graph: N = {N}, E = {E}; the published attention model's training logits (STEPS 3, "
+             f"AUX_LOSS_STEPS 2: {len(pe)} edge, {len(pn)} node, {len(pc)} class predictions), focal terms, threshold 0.5.", "",
+             "| form | ms |", "|---|---|",
+             f"| HIP (`pemp_amd.mpn_loss`) | {fmt(alone['hip'])} |",
+             f"| torch (`tests/loss_oracle.mpn_loss`, fp32) | {fmt(alone['torch'])} |", "",
+             f"Ratio torch / HIP: {alone['torch'][0] / alone['hip'][0]:.2f}. Acceptance (the HIP form faster than its "
+             f"torch form at this shape): {'met' if ok else 'NOT met'}.", "",
+             "Launches per forward + backward, HIP form (the library's event profiler, us per launch with the event "
+             "records' overhead inside): " + ", ".join(f"{k} x{n} ({us:.1f} us)" for k, (n, us) in sorted(launches.items()))
+             + f". torch form: {torch_kernels} kernels (torch.profiler, one forward + backward).", "",
+             "## The whole step: construct labels -> forward -> loss -> backward", "",
+             f"A labelled batch of c3's shape (B = {wl['B']}, {wl['H']} x {wl['W']}, synthetic ground truth, "
+             f"EDGE_LABEL_METHOD 6): N = {shape['N']}, E = {shape['E']}.", "",
+             "| loss | ms |", "|---|---|",
+             f"| HIP (`MPNLoss`) | {fmt(step['hip'])} |",
+             f"| torch (`tests/loss_oracle.mpn_loss`) | {fmt(step['torch'])} |", "",
+             f"Difference of the medians: {step['torch'][0] - step['hip'][0]:.3f} ms of {step['torch'][0]:.3f} ms. "
+             + ("The HIP median lies inside the torch form's own min .. max: at the whole step the difference is inside "
+                "the run-to-run spread." if inside else
+                "The HIP median lies outside the torch form's own min .. max.")]
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", default="step", choices=["step", "loss"], help="loss: the MPN loss leg alone")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=5, help="alternations of the unfused and the fused model step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_step.md"))
+    ap.add_argument("--out", default=None, help="profiles/train_step.md, or profiles/train_loss.md for --leg loss")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "train_loss.md" if args.leg == "loss" else "train_step.md")
     if not torch.cuda.is_available():
         raise SystemExit("train_bench: no HIP device (timings are taken on the GPU only)")
+    if args.leg == "loss":
+        return loss_leg(args)
     import bench
     from pemp_amd.mpn import train as tr
     from tests import train_oracle as to
