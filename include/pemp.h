@@ -842,6 +842,45 @@ int pemp_loss_fwd(const pemp_loss_rec* rec, void* workspace, size_t workspace_by
 int pemp_loss_bwd(const pemp_loss_rec* rec, const float* out, const float* grad_total, float* const* g_pe,
                   float* const* g_pn, float* const* g_pc, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The gradient of the node features x with respect to the maps they were read from (csrc/node_grad.hip): the
+ * backward of x[n] = features[b_n, :, y_n, x_n] and of x[n] = conv(raw)[b_n, :, y_n, x_n] (stride 1, square kernel
+ * k, zero padding pad; pemp_gather_projected_conv with one map of the conv output's size), with
+ * (x_n, y_n) = joint_det[n][0..1] and b_n = batch_index[n]. No float atomics; results are bitwise identical from
+ * call to call and depend on neither the grid nor the device.
+ *
+ * pemp_node_grad_pixels: dfeat [B][C][H][W] = per pixel the sum of the rows g[n][:] of the nodes on it, in ascending
+ *   n, left to right in fp32 from 0; every other element 0 (one hipMemsetAsync). sorted_keys [N] / perm [N] (int64):
+ *   the keys (b H + y) W + x of the nodes, sorted ascending by a stable sort, and the node of every sorted position;
+ *   a key outside [0, B H W) marks a node that lands nowhere. One wave per sorted position; the wave of a segment
+ *   head is the single writer of its pixel. Profiler label node_grad_pixels.
+ * pemp_node_conv_bwd: from g = dL/dx [N][Cout], each of draw [B][Cin][h][w], dW [Cout][Cin][k][k], db [Cout] that is
+ *   not NULL:
+ *     draw: D = g W2 [N][k k][Cin] (weight_khwc = the weight as [Cout][k][k][Cin]; one fma chain over co per
+ *           element), then the per-pixel sum of pemp_node_grad_pixels over the N k k rows of D with sorted_keys /
+ *           perm [N k k] keyed by the pixel ((b h + y - pad + dy) w + x - pad + dx; outside the map: any key outside
+ *           [0, B h w)), so a pixel's entries are added in ascending (n, dy, dx).
+ *     dW, db: the nodes are the reduction dimension, in node order: every chunk of 256 consecutive nodes is one fma
+ *           chain per element over the zero-padded input windows read from raw [B][Cin][h][w] and stores one partial
+ *           (Cout Cin k k + Cout floats) into `workspace`; the partials are added in a pairwise tree, 32 per pass
+ *           (the last group of a pass padded with zeros).
+ *   v_mfma_f32_16x16x4_f32 when Cin and Cout are multiples of 16, the same chains with fmaf otherwise. Limits as the
+ *   forward's: Cout <= 512, k <= 7 (PEMP_ERR_UNSUPPORTED beyond), 0 <= pad < k, Cin (k + 1)^2 floats within 64 KB,
+ *   every node on the conv's output map (one that is not, or whose batch_index is outside [0, B), adds nothing to dW).
+ *   Profiler labels node_conv_bwd, node_grad_pixels, node_conv_tree.
+ * pemp_node_conv_workspace_size(N, Cin, Cout, k): host arithmetic; D plus the partials of both tree buffers; 0 for
+ *   N <= 0 or arguments outside the limits.
+ * N == 0: the gradients that are not NULL are zero-filled, without a launch. Argument errors are reported before the
+ * first HIP call. Stream-ordered, no host synchronisation, no allocation (both entries may be captured).
+ * ---------------------------------------------------------------------------------------- */
+int pemp_node_grad_pixels(const float* g /*[N][C]*/, int64_t N, int C, const int64_t* sorted_keys, const int64_t* perm,
+                          int B, int H, int W, float* dfeat /*out [B][C][H][W]*/, void* stream);
+size_t pemp_node_conv_workspace_size(int64_t N, int Cin, int Cout, int ksize);
+int pemp_node_conv_bwd(const float* g /*[N][Cout]*/, const float* raw, const float* weight_khwc,
+                       const int64_t* joint_det /*[N][3]*/, const int64_t* batch_index /*[N]*/, int64_t N, int B, int Cin,
+                       int h, int w, int Cout, int ksize, int pad, const int64_t* sorted_keys, const int64_t* perm,
+                       float* draw, float* dW, float* db, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,14 +29,19 @@ def bind_mpn(model):
 
 
 _LOSS_NAMES = ("mpn_loss", "MPNLoss", "ClassMPNLossFactory", "mask_node_connections")
+_GATHER_NAMES = ("gather_nodes", "gather_nodes_conv", "PixelPlan")
 
 
 def __getattr__(name):
     """The training loss (loss.py): ``mpn_loss``, ``MPNLoss``, ``ClassMPNLossFactory``, ``mask_node_connections``;
+    the differentiable node features (node_gather.py): ``gather_nodes``, ``gather_nodes_conv``, ``PixelPlan``;
     imported on first use, like the entries above."""
     if name in _LOSS_NAMES:
         from . import loss as _l
         return getattr(_l, name)
+    if name in _GATHER_NAMES:
+        from . import node_gather as _g
+        return getattr(_g, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -173,6 +173,10 @@ SIGNATURES = {
     "pemp_loss_workspace_size": (c_sz, [c_i64, c_i64, c_i32, c_i32]),
     "pemp_loss_fwd": (c_i32, [ctypes.POINTER(PempLossRec), c_p, c_sz, c_p, c_p]),
     "pemp_loss_bwd": (c_i32, [ctypes.POINTER(PempLossRec), c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pemp_node_grad_pixels": (c_i32, [c_p, c_i64, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
+    "pemp_node_conv_workspace_size": (c_sz, [c_i64, c_i32, c_i32, c_i32]),
+    "pemp_node_conv_bwd": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p,
+                                   c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
 LABEL_OVERFLOW = 1                  # pemp.h PEMP_LABEL_OVERFLOW
 LABEL_CAND_DTYPE = [("g", "<i4"), ("n", "<u4"), ("sim", "<f8")]   # pemp.h pemp_label_cand

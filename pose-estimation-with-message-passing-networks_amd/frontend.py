@@ -69,6 +69,18 @@ class ProjectedMaps:
             self._wt_cache = cache = (key, wt, b)
         return cache[1], cache[2], g.kernel_size[0], g.padding[0]
 
+    def live_params(self):
+        """(weight, bias or None) of the gather conv as the optimizer's own parameters, fp32 (for the differentiable
+        x of node_gather.py; conv_params() above stays detached)."""
+        g = self.gather
+        return g.weight.float().contiguous(), None if g.bias is None else g.bias.float().contiguous()
+
+    def requires_grad(self):
+        """Whether a map or a parameter of the gather conv requires a gradient."""
+        g = self.gather
+        return any(m.requires_grad for m in self.maps) or (
+            g is not None and (g.weight.requires_grad or (g.bias is not None and g.bias.requires_grad)))
+
     def materialize(self):
         """The reference's dense map (for checks): sum of the projections / divisor, computed with the
         reference's own torch ops (feature_gather conv first when given)."""

@@ -79,13 +79,15 @@ class _Call:
     """What the host derives from one construct_graph call's inputs, filled once before the first launch: the detection
     half here (ahead of the count buffer), the graph half in graph() (the generator's first step). src_obj is the dense
     scoremaps or (proj) the pemp_proj_maps of a ProjectedHeatmaps; the features are dense (feats) or ProjectedMaps
-    (pmaps, pconv their feature_gather conv or None); the tags are absent, dense (tags) or projected (ptags)."""
+    (pmaps, pconv their feature_gather conv or None); the tags are absent, dense (tags) or projected (ptags). grad: how
+    x carries a gradient into the features (NaiveGraphConstructor._grad_kind; None: it does not), the tensors that take
+    it being feats, pmaps[0] and plive (the conv's live weight and bias)."""
     __slots__ = ("L", "st", "dev", "B", "J", "H", "W", "proj", "src_obj", "src", "detect", "masks", "use_thr", "topk",
                  "thr", "pool", "feats", "pmaps", "pconv", "divisor", "tags", "ptags", "C", "F", "A", "mode", "norm",
-                 "fully", "gkey", "counts_h")
+                 "fully", "gkey", "counts_h", "grad", "plive")
 
-    def __init__(self, gc, L, st):
-        self.L, self.st = L, st
+    def __init__(self, gc, L, st, grad=None):
+        self.L, self.st, self.grad, self.plive = L, st, grad, None
         sm = gc.scoremaps
         self.proj = isinstance(sm, ProjectedHeatmaps)   # the test front-end evaluated inside the detection
         if self.proj:
@@ -117,6 +119,8 @@ class _Call:
             pmaps = [m.float().contiguous() for m in feats.maps]
             C, divisor = feats.shape[1], feats.divisor
             pconv = feats.conv_params() if feats.gather is not None else None
+            if self.grad == "conv":
+                self.plive = feats.live_params()
             feats = None
         else:
             if feats.dtype != torch.float32:
@@ -446,8 +450,9 @@ class NaiveGraphConstructor:
         server, bench.py) queues the next batch before it collects the previous one, so the host's count wait overlaps
         its other work. A pending graph must be collected (result()) before another batch is started on the same
         stream twice over (the library's scratch is per device and stream)."""
+        grad = self._grad_kind()                    # (its refusals come before the library is touched)
         L = _lib.lib()
-        c = _Call(self, L, _lib.stream(self.device))
+        c = _Call(self, L, _lib.stream(self.device), grad)
         counts_ent = self._host_counts_take(L, c.dev, c.B)   # one read-back of the per-image counts (pemp_detect)
         pending = PendingGraph(self, self._construct(c, counts_ent[2][:c.B]), c.dev, counts_ent)
         pending._step()                             # up to the count wait: everything is queued
@@ -473,7 +478,8 @@ class NaiveGraphConstructor:
         the bound MPN in one call (pemp_step_fully_cap), every output in one buffer."""
         n_cap, e_cap = hint
         mpn = NaiveGraphConstructor._bound_mpn
-        bound = mpn is not None and c.J == getattr(mpn, "num_types", None) and getattr(mpn, "_cap_ok", True)
+        bound = (mpn is not None and c.J == getattr(mpn, "num_types", None) and getattr(mpn, "_cap_ok", True)
+                 and c.grad is None)     # (an x with a gradient is for a training step: nothing is queued behind it)
         mi = mpn._cap_info(c.C, c.A, n_cap, e_cap, c.dev) if bound else None
         plan = self._step_plan(c, cap, n_cap, e_cap, mi)
         flat = torch.empty(plan.struct.bytes, dtype=torch.uint8, device=c.dev)
@@ -578,8 +584,57 @@ class NaiveGraphConstructor:
             joint_tags = joint_tags.view((N,) + tuple(c.tags.shape[4:]) if c.tags.dim() > 4 else (N,))
         if c.ptags is not None and late_tags:
             joint_tags = self._gather_proj_tags(c, joint_det, batch_index, N)
+        if c.grad is not None:      # the filled x, now with its backward into the features (node_gather.py)
+            x = self._attach_grad(c, x, joint_det, batch_index)
         return (x, edge_attr, edge_index, None, None, None, None, joint_det, None, None, None, joint_scores,
                 batch_index, None, joint_tags)
+
+    _warned_projection = False   # the warning below was given (once per process)
+
+    def _grad_kind(self):
+        """How x is to carry a gradient into the features it is read from: None (no feature requires one, or grad mode
+        is off), "dense" (a features tensor), "maps" (ProjectedMaps without a conv) or "conv" (with its feature_gather
+        conv: the sparse path). Training never projects: more than one map, a size other than the map's own (the conv
+        output's) or a divisor other than 1 is refused when a map requires a gradient. Where only the conv's
+        parameters do, which is how every nn.Conv2d starts and how the test front-end has always been called outside
+        torch.no_grad(), the projecting call runs as before, x carries no gradient, and a warning says so once."""
+        f = self.features
+        if not torch.is_grad_enabled():
+            return None
+        if not isinstance(f, ProjectedMaps):
+            return "dense" if f.requires_grad else None
+        if not f.requires_grad():
+            return None
+        h, w = f.maps[0].shape[2:]
+        if f.gather is not None:
+            k, pad = f.gather.kernel_size[0], f.gather.padding[0]
+            h, w = h + 2 * pad - k + 1, w + 2 * pad - k + 1
+        why = None
+        if len(f.maps) != 1:
+            why = (f"ProjectedMaps with {len(f.maps)} maps: the differentiable x reads one map (training does not sum "
+                   "scales)")
+        elif (h, w) != f.size or f.divisor != 1.0:
+            why = (f"ProjectedMaps of size {f.size} with divisor {f.divisor} over a {(h, w)} map: the differentiable x "
+                   "does not project (the size must be the map's own, or the conv output's, and the divisor 1)")
+        if why is None:
+            return "maps" if f.gather is None else "conv"
+        if any(m.requires_grad for m in f.maps):
+            raise NotImplementedError(why + "; a map requires a gradient")
+        if not NaiveGraphConstructor._warned_projection:
+            NaiveGraphConstructor._warned_projection = True
+            import warnings
+            warnings.warn("pemp_amd: " + why + "; the gather conv's parameters require a gradient but x will carry "
+                          "none (freeze them, or call under torch.no_grad(), to silence this)", stacklevel=3)
+        return None
+
+    @staticmethod
+    def _attach_grad(c, x, joint_det, batch_index):
+        """x as the output of the autograd function of its read (the values are the build's, untouched)."""
+        from . import node_gather as ng
+        if c.grad == "conv":
+            return ng._GatherNodesConv.apply(c.pmaps[0], c.plive[0], c.plive[1], joint_det, batch_index, c.pconv[3], x,
+                                             c.pconv[0], None)
+        return ng._GatherNodes.apply(c.feats if c.grad == "dense" else c.pmaps[0], joint_det, batch_index, x, None)
 
     def _build_generic(self, c, dets, cap, counts_l, N):
         """Offsets, node pack, then the graph type's edges and their features, a launch each (knn, feature_knn,
