@@ -107,6 +107,12 @@ int pemp_detect_projected(const pemp_proj_maps* maps, const float* masks, int B,
                           int pool_kernel, float threshold, int use_threshold, int topk, int stages,
                           void* workspace, size_t workspace_bytes, int64_t* det_xyt, float* det_scores,
                           int32_t* n_det, int cap, int32_t* n_det_host, void* stream);
+/* Which loader pemp_detect_projected's NMS pass takes for S scales of h[s] x w[s] projected to H x W with this
+ * pool_kernel (host arithmetic only, no device call; for tests): 1 = the generic per-pixel loader, 2 = the separable
+ * one (every unit's rows span at most 16 staged low-resolution rows of every scale); < 0 on bad arguments.
+ * *x2_bands (optional): the bands of 16 rows in which scale 0 takes the separable loader's exact-2x register path
+ * (h[0] * 2 == H and no clamped row in the band's halo); 0 with the generic loader. */
+int pemp_detect_projected_path(const int* h, const int* w, int S, int H, int W, int pool_kernel, int32_t* x2_bands);
 /* The same maps materialised (refine / adjust need the image-size maps; checks): scoremaps [B,J,H,W]
  * (or NULL) and tags (or NULL) as F planes [F][B,J,H,W] (f = 0 forward, 1 flipped pass), F = 2 with a
  * flipped pass. Values identical to the ones the detection samples. */

@@ -111,6 +111,7 @@ SIGNATURES = {
                                            c_f32, c_p, c_p, c_i64, c_p, c_p]),
     "pemp_detect_projected": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_i32, c_p,
                                       c_sz, c_p, c_p, c_p, c_i32, c_p, c_p]),
+    "pemp_detect_projected_path": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "pemp_gather_projected_tags": (c_i32, [c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_i64, c_p, c_p]),
     "pemp_project_maps": (c_i32, [c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
     "pemp_stage_merge": (c_i32, [c_p, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),

@@ -461,6 +461,11 @@ __device__ __forceinline__ void proj_x2_first(const ProjArgs& pj, const DetectGe
   }
 }
 
+// does the band at row y0 take proj_x2_first for a first scale of h0 rows? The loader's branch and the host's
+// pemp_detect_projected_path share this one statement. (A macro: as an inline function the same test left the strip
+// kernels with another instruction schedule, and their code is kept as timed.)
+#define PROJ_X2_BAND(h0, H, P, y0) ((h0) * 2 == (H) && (y0) - (P) >= 1 && (y0) + SR - 1 + (P) <= (H) - 3)
+
 template <int P>
 __device__ __forceinline__ void load_unit_proj_sep(const ProjArgs& pj, const DetectGeom& g, int u,
                                                    float (&r)[SR + 2 * P], float* __restrict__ stage) {
@@ -470,7 +475,7 @@ __device__ __forceinline__ void load_unit_proj_sep(const ProjArgs& pj, const Det
   const int y0 = q.band * SR, x = q.strip * g.sc - P + lane;
   const bool xok = x >= 0 && x < g.W;
   const int xc = min(max(x, 0), g.W - 1);
-  if (pj.h[0] * 2 == g.H && y0 - P >= 1 && y0 + SR - 1 + P <= g.H - 3) {   // (uniform)
+  if (PROJ_X2_BAND(pj.h[0], g.H, P, y0)) {   // (uniform)
     if (pj.f[0]) proj_x2_first<P, true>(pj, g, b, j, y0, xc, r);
     else proj_x2_first<P, false>(pj, g, b, j, y0, xc, r);
   } else if (pj.f[0]) {
@@ -1598,6 +1603,28 @@ extern "C" int pemp_detect_projected(const pemp_proj_maps* maps, const float* ma
   if (const int rc = proj_args(maps, J, &pj, "pemp_detect_projected")) return rc;
   return detect_impl(nullptr, &pj, masks, B, J, H, W, pool_kernel, threshold, use_threshold, topk, stages, workspace,
                      workspace_bytes, det_xyt, det_scores, n_det, cap, n_det_host, stream);
+}
+
+extern "C" int pemp_detect_projected_path(const int* h, const int* w, int S, int H, int W, int pool_kernel,
+                                          int32_t* x2_bands) {
+  PEMP_CHECK_ARG(h && w && S >= 1 && S <= PEMP_PROJ_MAXS && H > 0 && W > 0,
+                 "pemp_detect_projected_path: bad args (1..%d scales, H, W > 0)", PEMP_PROJ_MAXS);
+  PEMP_CHECK_ARG(pool_kernel % 2 == 1 && pool_kernel >= 1 && pool_kernel / 2 <= MAXR,
+                 "pemp_detect_projected_path: pool_kernel must be odd and <= %d (got %d)", 2 * MAXR + 1, pool_kernel);
+  ProjArgs pj{};
+  pj.S = S;
+  for (int s = 0; s < S; ++s) {
+    PEMP_CHECK_ARG(h[s] > 0 && w[s] > 0, "pemp_detect_projected_path: scale %d: empty size", s);
+    pj.h[s] = h[s];
+    pj.w[s] = w[s];
+  }
+  const DetectGeom g = geom(1, 1, H, W, pool_kernel, 1);
+  const bool sep = proj_sep_ok(pj, g);
+  if (x2_bands) {
+    *x2_bands = 0;
+    for (int band = 0; sep && band < g.nb; ++band) *x2_bands += PROJ_X2_BAND(pj.h[0], g.H, g.p, band * SR);
+  }
+  return sep ? 2 : 1;
 }
 
 extern "C" int pemp_project_maps(const pemp_proj_maps* maps, int B, int J, int H, int W, int tag_scale,
