@@ -573,8 +573,8 @@ int pemp_mpn_graph_stats(uint64_t* out3);
 int pemp_edge_cus_policy(int num_cus, int64_t E, int reserve_request);
 
 /* sizeof of the ABI structs as this library was built (host only; bindings check their mirrors against it):
- * which = 0 pemp_mpn_weights, 1 pemp_mpn_desc, 2 pemp_mlp, 3 pemp_proj_maps, 4 pemp_step_plan, 5 pemp_loss_rec; 0 for
- * any other value. */
+ * which = 0 pemp_mpn_weights, 1 pemp_mpn_desc, 2 pemp_mlp, 3 pemp_proj_maps, 4 pemp_step_plan, 5 pemp_loss_rec, 6
+ * pemp_kp_loss_rec; 0 for any other value. */
 size_t pemp_abi_struct_size(int which);
 
 /* pemp_mpn_forward for an edge_index sorted by (src, dst) without duplicates and symmetric (every s -> d has
@@ -886,6 +886,78 @@ int pemp_node_conv_bwd(const float* g /*[N][Cout]*/, const float* raw, const flo
                        const int64_t* joint_det /*[N][3]*/, const int64_t* batch_index /*[N]*/, int64_t N, int B, int Cin,
                        int h, int w, int Cout, int ksize, int pad, const int64_t* sorted_keys, const int64_t* perm,
                        float* draw, float* dW, float* db, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The keypoint losses (csrc/kp_loss.hip): the heatmap and associative-embedding terms of ClassMultiLossFactory
+ * (Utils/loss.py:641-665; HeatmapLoss :17-27, AELoss :37-98) over S <= 4 stages, fused each way. Per stage s:
+ * pred [B, C, H, W] with C >= J, gt [B, J, H, W], mask [B, H, W] (any float values), tag [B, P, J, 2] int32 rows
+ * (index, visible) as JointsGenerator writes them (data/utils.py:4-27); all contiguous, fp32 unless said.
+ *   heatmap = sum_s [with_heatmap] heatmap_factor_s / (B J H W) sum_{b, j, y, x} (pred[b, j] - gt[b, j])^2 mask[b]
+ *             over the first J planes of pred, read in place (image stride C H W)
+ *   ae      = sum_s [with_ae] (push_factor_s mean_b push_b + pull_factor_s mean_b pull_b), where the tags of image b
+ *             are t = pred[b, J:] flattened (T = (C - J) H W values) and a person p with n_p >= 1 entries of
+ *             visible > 0 and index in [0, T) has m_p = mean(t_i), pull_p = mean((t_i - m_p)^2); with P' such persons
+ *             pull_b = sum_p pull_p / P'; push_b = 0.5 (sum_{p, q} f(m_p - m_q) - P') / ((P' - 1) P') for P' >= 2 over
+ *             all ordered pairs (diagonal included), f(d) = exp(-d^2) (PEMP_KP_AE_EXP) or max(0, 1 - |d|)
+ *             (PEMP_KP_AE_MAX); P' = 1: push_b = 0; P' = 0: both 0 and no gradient
+ *   total   = heatmap + ae
+ * A visible entry whose index lies outside [0, T) is skipped and counted (the reference raises IndexError there).
+ * Limits: S <= 4, P <= 32, J <= 32 (PEMP_ERR_UNSUPPORTED beyond); C H W < 2^31 per image.
+ *
+ * pemp_kp_loss_fwd: out [PEMP_KP_OUT] floats: out[0..2] = heatmap, ae, total; out[3 + 3 s + 0..2] the heatmap, push and
+ *   pull parts of stage s (factors applied). Two launches (labels kp_loss_fwd, kp_loss_reduce). Heatmap blocks: a
+ *   stage's blocks (one per PEMP_KP_CHUNK elements of an image's J H W heatmap values, at most PEMP_KP_MAXBLOCKS, the
+ *   rest strided) found through the prefix table `blk0`; 16-byte loads when H W is a multiple of 4 and pred, gt and
+ *   mask are 16-byte aligned, scalar ones otherwise; fp32 inside a thread's 16 elements and through the wave, fp64
+ *   from there on; one fp64 partial per block. AE blocks, one per (stage, image), in the same launch: the P J tags
+ *   gathered into LDS, everything after the gather in fp64; they leave push_b, pull_b, m_p, n_p, P' and the count of
+ *   skipped entries in the workspace. The reduction is one block that adds the partials in a fixed order in fp64 and
+ *   writes the skipped-entry count of the call to the int32 at the start of the workspace (the status word: 0 when
+ *   every visible index was in range). No atomics on floats; bitwise reproducible; the order depends on the record.
+ * pemp_kp_loss_bwd: g_pred[s] [B, C, H, W] (a host array of PEMP_KP_MAXS device pointers; NULL entries are skipped) =
+ *   d total / d pred[s] times the device scalar grad_total[0] (NULL: 1), every element written exactly once: launch
+ *   one (label kp_loss_bwd) writes 2 (pred - gt) mask heatmap_factor / (B J H W) to the heatmap planes, recomputed
+ *   from pred, gt and mask, and zeros to the tag planes; launch two (label kp_loss_bwd_tags, behind it in stream
+ *   order, one block per (stage, image) with with_ae) writes the listed tag entries from m_p, n_p, P' of the forward's
+ *   workspace. An index listed more than once in an image (two persons on one pixel and joint) gets the sum of its
+ *   entries in ascending (person, joint) order, in fp32 from the first, written by the lane of the first entry.
+ *   `workspace` is the forward's, unchanged since (a caller that interleaves calls keeps one workspace per call).
+ * Neither entry synchronises or allocates. Argument errors are reported before any launch.
+ * pemp_kp_loss_workspace_size is host arithmetic over the record's sizes and flags (pointers are not read): 256 bytes
+ *   of status, the block partials, and per (stage, image) 2 doubles + 2 int32 + P (double + int32), each array
+ *   256-byte aligned; 0 for a record outside the limits.
+ * ---------------------------------------------------------------------------------------- */
+#define PEMP_KP_MAXS 4
+#define PEMP_KP_MAXP 32
+#define PEMP_KP_MAXJ 32
+#define PEMP_KP_CHUNK 4096
+#define PEMP_KP_MAXBLOCKS 2048
+#define PEMP_KP_OUT 16
+enum { PEMP_KP_AE_EXP = 0, PEMP_KP_AE_MAX = 1 };
+typedef struct pemp_kp_stage {
+  const float* pred;                /* [B, C, H, W] */
+  const float* gt;                  /* [B, J, H, W]; read with with_heatmap */
+  const float* mask;                /* [B, H, W]; read with with_heatmap */
+  const int32_t* tag;               /* [B, P, J, 2]; read with with_ae */
+  int32_t C, H, W;
+  int32_t with_heatmap, with_ae;    /* HRNET.LOSS.WITH_HEATMAPS_LOSS[s], TRAIN.WITH_AE_LOSS[s] */
+  float heatmap_factor, push_factor, pull_factor;
+} pemp_kp_stage;
+typedef struct pemp_kp_loss_rec {
+  int32_t S, B, J, P;
+  int32_t ae_kind;                  /* PEMP_KP_AE_EXP / PEMP_KP_AE_MAX */
+  int32_t pad_;
+  pemp_kp_stage stage[PEMP_KP_MAXS];
+  int32_t blk0[PEMP_KP_MAXS + 2];   /* filled by the library on its copy of the record (callers leave it): [s] the
+                                       first of stage s's streaming blocks (counted from 0), [PEMP_KP_MAXS] their
+                                       number, [PEMP_KP_MAXS + 1] the grid; the forward's AE blocks come first in
+                                       the grid, the streaming blocks behind them */
+} pemp_kp_loss_rec;
+size_t pemp_kp_loss_workspace_size(const pemp_kp_loss_rec* rec);
+int pemp_kp_loss_fwd(const pemp_kp_loss_rec* rec, void* workspace, size_t workspace_bytes, float* out /*[PEMP_KP_OUT]*/,
+                     void* stream);
+int pemp_kp_loss_bwd(const pemp_kp_loss_rec* rec, const void* workspace, const float* grad_total,
+                     float* const* g_pred /*[PEMP_KP_MAXS]*/, void* stream);
 
 #ifdef __cplusplus
 }

@@ -29,16 +29,21 @@ def bind_mpn(model):
 
 
 _LOSS_NAMES = ("mpn_loss", "MPNLoss", "ClassMPNLossFactory", "mask_node_connections")
+_KP_LOSS_NAMES = ("keypoint_loss", "KeypointLoss", "ClassMultiLossFactory")
 _GATHER_NAMES = ("gather_nodes", "gather_nodes_conv", "PixelPlan")
 
 
 def __getattr__(name):
     """The training loss (loss.py): ``mpn_loss``, ``MPNLoss``, ``ClassMPNLossFactory``, ``mask_node_connections``;
+    the keypoint losses (kp_loss.py): ``keypoint_loss``, ``KeypointLoss``, ``ClassMultiLossFactory``;
     the differentiable node features (node_gather.py): ``gather_nodes``, ``gather_nodes_conv``, ``PixelPlan``;
     imported on first use, like the entries above."""
     if name in _LOSS_NAMES:
         from . import loss as _l
         return getattr(_l, name)
+    if name in _KP_LOSS_NAMES:
+        from . import kp_loss as _k
+        return getattr(_k, name)
     if name in _GATHER_NAMES:
         from . import node_gather as _g
         return getattr(_g, name)

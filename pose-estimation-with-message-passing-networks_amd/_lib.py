@@ -79,6 +79,21 @@ class PempLossRec(ctypes.Structure):
                 ("node_classes", c_p), ("edge_mask", c_p * LOSS_MAXKE)]
 
 
+KP_MAXS, KP_MAXP, KP_MAXJ, KP_CHUNK, KP_MAXBLOCKS, KP_OUT = 4, 32, 32, 4096, 2048, 16   # pemp.h PEMP_KP_*
+KP_AE_EXP, KP_AE_MAX = 0, 1
+
+
+class PempKpStage(ctypes.Structure):
+    _fields_ = [("pred", c_p), ("gt", c_p), ("mask", c_p), ("tag", c_p), ("C", c_i32), ("H", c_i32), ("W", c_i32),
+                ("with_heatmap", c_i32), ("with_ae", c_i32), ("heatmap_factor", c_f32), ("push_factor", c_f32),
+                ("pull_factor", c_f32)]
+
+
+class PempKpLossRec(ctypes.Structure):
+    _fields_ = [("S", c_i32), ("B", c_i32), ("J", c_i32), ("P", c_i32), ("ae_kind", c_i32), ("pad_", c_i32),
+                ("stage", PempKpStage * KP_MAXS), ("blk0", c_i32 * (KP_MAXS + 2))]
+
+
 # name -> (restype, argtypes); every symbol of include/pemp.h
 SIGNATURES = {
     "pemp_abi_version": (c_i32, []),
@@ -174,6 +189,9 @@ SIGNATURES = {
     "pemp_loss_workspace_size": (c_sz, [c_i64, c_i64, c_i32, c_i32]),
     "pemp_loss_fwd": (c_i32, [ctypes.POINTER(PempLossRec), c_p, c_sz, c_p, c_p]),
     "pemp_loss_bwd": (c_i32, [ctypes.POINTER(PempLossRec), c_p, c_p, c_p, c_p, c_p, c_p]),
+    "pemp_kp_loss_workspace_size": (c_sz, [ctypes.POINTER(PempKpLossRec)]),
+    "pemp_kp_loss_fwd": (c_i32, [ctypes.POINTER(PempKpLossRec), c_p, c_sz, c_p, c_p]),
+    "pemp_kp_loss_bwd": (c_i32, [ctypes.POINTER(PempKpLossRec), c_p, c_p, c_p, c_p]),
     "pemp_node_grad_pixels": (c_i32, [c_p, c_i64, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
     "pemp_node_conv_workspace_size": (c_sz, [c_i64, c_i32, c_i32, c_i32]),
     "pemp_node_conv_bwd": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p,

@@ -1,4 +1,5 @@
-"""Configuration surface of the hot path: the reference's ``MODEL.GC.*`` / ``MODEL.MPN.*`` / ``MODEL.LOSS.*`` keys.
+"""Configuration surface of the hot path: the reference's ``MODEL.GC.*`` / ``MODEL.MPN.*`` / ``MODEL.LOSS.*`` keys and
+the ``MODEL.KP`` / ``MODEL.HRNET.LOSS.*`` / ``TRAIN.WITH_AE_LOSS`` keys of the keypoint losses.
 
 Restates the defaults of ``src/config/default_config.py:30-46, 112-165`` (yacs is not a dependency here)
 with a small attribute-dict ``CfgNode`` that reads the reference's experiment YAMLs
@@ -64,6 +65,13 @@ def _coerce(v, cur):
 def _defaults():
     return {
         "MODEL": {
+            # default_config.py:23, 53, 61, 71-78: what the keypoint losses read (kp_loss.py)
+            "KP": "hrnet",
+            "HG": {"NSTACK": 4},
+            "HRNET": {"NUM_JOINTS": 17,
+                      "LOSS": {"NUM_STAGES": 2, "WITH_HEATMAPS_LOSS": (True, True), "HEATMAPS_LOSS_FACTOR": (1.0, 1.0),
+                               "WITH_AE_LOSS": (True, False), "AE_LOSS_TYPE": "exp",
+                               "PUSH_LOSS_FACTOR": (0.001, 0.001), "PULL_LOSS_FACTOR": (0.001, 0.001)}},
             # default_config.py:30-46; new keys allowed for LOSS_WEIGHTS, which the experiment files add (:31)
             "LOSS": CfgNode({
                 "NAME": ["edge_loss"], "NODE_WEIGHT": 1.0, "EDGE_WEIGHT": 1.0, "CLASS_WEIGHT": 1.0, "TAG_WEIGHT": 1.0,
@@ -93,6 +101,7 @@ def _defaults():
         },
         "DATASET": {"NUM_JOINTS": 17, "MAX_NUM_PEOPLE": 30, "SIGMA": 2, "INPUT_SIZE": 512},
         "TEST": {"SCALE_FACTOR": [1.0]},
+        "TRAIN": {"END_TO_END": False, "WITH_AE_LOSS": [False, False]},     # default_config.py:236, 243
     }
 
 

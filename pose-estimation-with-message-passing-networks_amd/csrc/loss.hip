@@ -46,15 +46,6 @@ Grid grid_for(int64_t N, int64_t E, int K_n) {
   return g;
 }
 
-// sum over the 64 lanes, in every lane: the in-row DPP steps of wave_sum_i32, then the row swaps
-__device__ __forceinline__ float wave_sum_f32(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));   // row_mirror
-  return xsum_rows(v);
-}
-
 // (1 - pt)^gamma off the multiply form; kept out of line: 32 inlined copies of powf would be most of the kernel
 __device__ __noinline__ float pow_gamma(float q, float gamma) { return powf(q, gamma); }
 
@@ -295,13 +286,6 @@ __global__ __launch_bounds__(kBlock) void loss_fwd_kernel(pemp_loss_rec r, int n
   if (lane == 0) sh[wave][0] = accF, sh[wave][1] = accM, sh[wave][2] = accC;
   __syncthreads();
   if (tid < kNodeSlots) npart[(size_t)nb * kNodeSlots + tid] = (sh[0][tid] + sh[1][tid]) + (sh[2][tid] + sh[3][tid]);
-}
-
-// sum over the wave in fp64, fixed tree, in every lane
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // One block. Slot sums in fp64 (a wave per slot: lane l adds blocks l, l + 64, ... in order, then the lane tree), then

@@ -4625,6 +4625,7 @@ extern "C" size_t pemp_abi_struct_size(int which) {
     case 3: return sizeof(pemp_proj_maps);
     case 4: return sizeof(pemp_step_plan);
     case 5: return sizeof(pemp_loss_rec);
+    case 6: return sizeof(pemp_kp_loss_rec);
     default: return 0;
   }
 }

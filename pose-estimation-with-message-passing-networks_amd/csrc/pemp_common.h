@@ -156,5 +156,19 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
   const auto b = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
   return (int)(b[0] + b[1]);
 }
+// sum over the 64 lanes, in every lane: the in-row DPP steps of wave_sum_i32, then the row swaps
+__device__ __forceinline__ float wave_sum_f32(float v) {
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));    // quad_perm [1,0,3,2]
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));    // quad_perm [2,3,0,1]
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));   // row_half_mirror
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));   // row_mirror
+  return xsum_rows(v);
+}
+// sum over the wave in fp64, fixed tree, in every lane
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 }  // namespace pemp
