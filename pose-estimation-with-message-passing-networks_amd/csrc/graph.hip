@@ -643,7 +643,6 @@ __global__ __launch_bounds__(1024) void knn_emit_rows_kernel(KnnEmitArgs k) {
   int64_t pos = before + k.rowstart[src];
   int64_t sx = 0, sy = 0;
   int ts = 0;
-  float tsrc = 0.f;
   if (k.edge_attr) { sx = nx[a]; sy = ny[a]; ts = nt[a]; }
   for (int w = 0; w < wpr; ++w) {
     const unsigned long long word = k.R[src * KNN_W + w];

@@ -17,6 +17,8 @@
 // MFMA: v_mfma_f32_16x16x4_f32 (exact fp32). Fragment convention per wave: item (edge or node)
 // c = lane & 15 on the MFMA N dimension, features 16*blk + 4*(lane >> 4) + r in registers, so one
 // layer's accumulator is the next layer's B operand with no data movement.
+// The edge-order prepares (the first kernels of a forward) are in mpn_order.hip, reached through the launch functions
+// of mpn_internal.h; mpn_order.h holds what the closed-form prepare shares with launch A of the paired prelude here.
 #include <limits.h>
 
 #include <algorithm>
@@ -29,43 +31,11 @@
 #include <string.h>
 #include <math.h>
 
-#include "pemp_common.h"
+#include "mpn_internal.h"
+#include "mpn_order.h"
 
 namespace pemp {
 namespace {
-
-constexpr int D = 64;
-constexpr int LDW = 72;     // LDS row stride of a 64x64 weight tile (conflict-free ds_read_b128)
-constexpr int MAXT = 17;
-constexpr int EDGE_WAVES = 16;   // waves per edge-pass workgroup (one workgroup per CU)
-// edge embedding: EMB_WAVES waves per workgroup, EMB_PER_CU workgroups per CU (each with its own LDS image; the
-// register target follows: EMB_WAVES x EMB_PER_CU / 4 waves per SIMD)
-// (10 x 2 and 8 x 2 measured against 16 x 1 in round 6, profiles/r06_embed_two_wg.md: not faster)
-constexpr int EMB_WAVES = 16, EMB_PER_CU = 1;
-constexpr int EMB_MIN_WAVES_EU = EMB_WAVES * EMB_PER_CU / 4 > 1 ? EMB_WAVES * EMB_PER_CU / 4 : 1;
-// CUs that the one-workgroup-per-CU launches of a forward over E edges (edge passes, edge embedding, and the prepares'
-// per-workgroup split) spread over. From RESERVE_MIN_EDGES edges on, PEMP_RESERVE_CUS of them (rounded down to
-// a multiple of 8, so the XCD-aware placement still sees whole XCD rows) are left free: with two batches in flight
-// the other batch's small latency-bound kernels run there instead of waiting for the full-chip launches (c3 +4 %,
-// c3knn10 / c5ms +11 % images/s, one batch at a time -1.5 %). Smaller graphs (batch 1) keep
-// every CU. The edge embedding leaves the reserved CUs free too (spread over every CU: serial steps +1 % / +3.4 %,
-// two batches in flight slower).
-constexpr int RESERVE_CUS_DEFAULT = 64;        // (the PEMP_RESERVE_CUS environment variable overrides it)
-constexpr int64_t RESERVE_MIN_EDGES = 65536;   // (batch 1 stays below it: one batch at a time lost 1.5 % to a reservation)
-// The reservation is capped at a quarter of the device (rounded down to a multiple of 8): 64 of the MI355X's 256
-// CUs, less on a smaller device or a compute partition, where a fixed 64 would take most of the chip.
-static int edge_cus_policy(int cus, int64_t E, int request) {
-  if (E < RESERVE_MIN_EDGES || cus <= 8) return cus;
-  const int r = std::min(std::max(request, 0), cus / 4) & ~7;
-  return cus - r;
-}
-static int edge_cus(int64_t E) {
-  static const int request = [] {
-    const char* e = getenv("PEMP_RESERVE_CUS");
-    return e ? atoi(e) : RESERVE_CUS_DEFAULT;
-  }();
-  return edge_cus_policy(num_cus(), E, request);
-}
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float a, float b, float c, float d) {
@@ -151,274 +121,6 @@ __device__ __forceinline__ void mlp_frag(const pemp_mlp& m, float (&a)[MAXB][4],
     for (int x = 0; x < MAXB; ++x)
 #pragma unroll
       for (int r = 0; r < 4; ++r) a[x][r] = b[x][r];
-  }
-}
-
-// ---- segmented scans across the 16 items of a wave tile (lanes c = lane & 15) ----
-struct SegMask {
-  bool f1, f2, f4, f8, b1, b2, b4, b8;
-};
-
-__device__ __forceinline__ SegMask seg_mask(int seg, int c) {
-  // every lane must execute every shuffle (a lane masked off by a short-circuit would feed
-  // garbage to the lane that reads it), so evaluate the shuffles before the comparisons
-  const int u1 = __shfl_up(seg, 1, 16), u2 = __shfl_up(seg, 2, 16);
-  const int u4 = __shfl_up(seg, 4, 16), u8 = __shfl_up(seg, 8, 16);
-  const int d1 = __shfl_down(seg, 1, 16), d2 = __shfl_down(seg, 2, 16);
-  const int d4 = __shfl_down(seg, 4, 16), d8 = __shfl_down(seg, 8, 16);
-  SegMask m;
-  m.f1 = c >= 1 && u1 == seg;
-  m.f2 = c >= 2 && u2 == seg;
-  m.f4 = c >= 4 && u4 == seg;
-  m.f8 = c >= 8 && u8 == seg;
-  m.b1 = c + 1 < 16 && d1 == seg;
-  m.b2 = c + 2 < 16 && d2 == seg;
-  m.b4 = c + 4 < 16 && d4 == seg;
-  m.b8 = c + 8 < 16 && d8 == seg;
-  return m;
-}
-
-__device__ __forceinline__ float scan_add(float v, const SegMask& m) {
-  float o;
-  o = __shfl_up(v, 1, 16); if (m.f1) v += o;
-  o = __shfl_up(v, 2, 16); if (m.f2) v += o;
-  o = __shfl_up(v, 4, 16); if (m.f4) v += o;
-  o = __shfl_up(v, 8, 16); if (m.f8) v += o;
-  return v;
-}
-
-__device__ __forceinline__ float scan_max(float v, const SegMask& m) {
-  float o;
-  o = __shfl_up(v, 1, 16); if (m.f1) v = fmaxf(v, o);
-  o = __shfl_up(v, 2, 16); if (m.f2) v = fmaxf(v, o);
-  o = __shfl_up(v, 4, 16); if (m.f4) v = fmaxf(v, o);
-  o = __shfl_up(v, 8, 16); if (m.f8) v = fmaxf(v, o);
-  return v;
-}
-
-__device__ __forceinline__ float scan_max_bwd(float v, const SegMask& m) {
-  float o;
-  o = __shfl_down(v, 1, 16); if (m.b1) v = fmaxf(v, o);
-  o = __shfl_down(v, 2, 16); if (m.b2) v = fmaxf(v, o);
-  o = __shfl_down(v, 4, 16); if (m.b4) v = fmaxf(v, o);
-  o = __shfl_down(v, 8, 16); if (m.b8) v = fmaxf(v, o);
-  return v;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Workspace
-// ---------------------------------------------------------------------------------------------
-struct MpnWs {
-  int *cnt, *seg, *wg_start, *perm, *s_src, *s_dst, *s_orig, *err, *sym;
-  float *X, *NT, *agg, *Q0, *EA, *EB, *img, *eimg;
-  int4* ranges;
-};
-
-constexpr int IMG_FLOATS = 112 * 1024;  // >= LDS image of a node embedding (<= 4 layers, <= 128 wide) + both heads (<= 64 wide)
-constexpr int EIMG_MAX_STRIDE = 4 * D * LDW + (2 * D + 4) + (D + 32) * LDW + D + 32 + 32 + 4;   // edge image floats per type (max)
-
-// order_offs (pemp_mpn_order_layout): the byte offsets of seg, wg_start, s_src, s_dst and s_orig
-static MpnWs mpn_carve(void* base, int T, int64_t N, int64_t E, size_t* bytes, size_t* order_offs = nullptr) {
-  Carver c(base);
-  MpnWs w;
-  size_t oo[5];
-  const int64_t K = (int64_t)T * N;
-  w.err = c.take<int>(64);               // err[0..3] then cnt: zeroed together
-  w.cnt = w.err + 64;
-  c.take<int>(K + 1);
-  w.seg = c.take<int>(K + 1);
-  oo[0] = c.last;
-  w.wg_start = c.take<int>(MAXT + 2);
-  oo[1] = c.last;
-  w.perm = c.take<int>(E);
-  w.s_src = c.take<int>(E);
-  oo[2] = c.last;
-  w.s_dst = c.take<int>(E);
-  oo[3] = c.last;
-  w.s_orig = c.take<int>(E);
-  oo[4] = c.last;
-  if (order_offs) std::copy(oo, oo + 5, order_offs);
-  w.X = c.take<float>(N * 128);
-  w.NT = c.take<float>(N * (128 + 64 * (int64_t)T));
-  w.agg = c.take<float>(N * T * D);
-  w.Q0 = c.take<float>(E * D);
-  w.EA = c.take<float>(E * D);
-  w.EB = c.take<float>(E * D);
-  w.img = c.take<float>(IMG_FLOATS);
-  const int G = std::max(num_cus(), T);        // edge-pass grid (at most)
-  w.ranges = c.take<int4>((size_t)G * (EDGE_WAVES + 12));
-  w.eimg = c.take<float>((size_t)T * EIMG_MAX_STRIDE);   // edge-pass weight image when the caller has none
-  w.sym = c.take<int>(3 * N);                           // symmetric prepare: row bounds + check flags per node
-  if (bytes) *bytes = c.used;
-  return w;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Prepare: type-major counting sort of the edges (deterministic: ties kept in edge-id order)
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mpn_count_kernel(const int64_t* __restrict__ ei, const int64_t* __restrict__ types,
-                                                        int64_t ts, int64_t N, int64_t E, int T, int* __restrict__ cnt,
-                                                        int* __restrict__ err) {
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t s = ei[e], d = ei[E + e];
-    if (s < 0 || s >= N || d < 0 || d >= N) { atomicOr(err, 1); continue; }
-    const int64_t t = T == 1 ? 0 : types[s * ts];   // MPLayer (one message MLP) ignores types
-    if (t < 0 || t >= T) { atomicOr(err, 2); continue; }
-    atomicAdd(&cnt[t * N + d], 1);
-  }
-}
-
-
-
-// Split G edge-pass workgroups (one per CU) over the types so that the largest share, in 16-edge tiles per
-// workgroup, is as small as possible: L = the least tile load with sum_t ceil(tiles_t / L) <= G, then
-// gt = ceil(tiles_t / L) (>= 1 per non-empty type; sum <= G, spare workgroups get no range). The kernel's time is
-// its busiest CU's, so this, not proportional shares, is the balanced split. tstart[t] (LDS, t <= T) = first edge
-// of type t; gt = LDS scratch [MAXT]. Wave 0 does the search (T <= MAXT < 64); block-wide (contains
-// __syncthreads).
-__device__ void type_split(const int* tstart, int64_t etot, int T, int G, int* gt, int* wg_start) {
-  (void)etot;
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    const int tiles = lane < T ? (tstart[lane + 1] - tstart[lane] + 15) / 16 : 0;
-    int hi = tiles;
-    for (int o = 32; o >= 1; o >>= 1) hi = max(hi, __shfl_xor(hi, o));
-    int lo = 1;
-    hi = max(hi, 1);
-    while (lo < hi) {   // (uniform)
-      const int mid = (lo + hi) >> 1;
-      int need = tiles > 0 ? (tiles + mid - 1) / mid : 0;
-      for (int o = 32; o >= 1; o >>= 1) need += __shfl_xor(need, o);
-      if (need <= G) hi = mid;
-      else lo = mid + 1;
-    }
-    const int share = tiles > 0 ? (tiles + lo - 1) / lo : 0;
-    int incl = share;   // inclusive prefix over the types
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(incl, o);
-      if (lane >= o) incl += v;
-    }
-    if (lane < T) {
-      gt[lane] = share;
-      wg_start[lane + 1] = incl;
-    }
-    if (lane == 0) wg_start[0] = 0;
-  }
-  __syncthreads();
-}
-
-// the edge-step grid (wg_start). One 1024-thread block, 16 contiguous counts per thread per pass
-// (all loads of a pass in flight together), carry across passes. The per-type segment starts
-// seg[t*N] are captured from LDS on the way out (no read-back of seg).
-constexpr int SCAN_SPT = 16;
-// With `flags` (the symmetric prepare, which has no zeroing launch): err[0..3] are written here, err[0] = the OR of
-// flags[0..nflags) | 4 if the counts do not sum to E_all.
-__global__ __launch_bounds__(1024) void mpn_scan_kernel(const int* __restrict__ cnt, int64_t K, int64_t N, int T,
-                                                        int G, int* __restrict__ seg, int* __restrict__ wg_start,
-                                                        const int* __restrict__ flags = nullptr, int64_t nflags = 0,
-                                                        int64_t E_all = 0, int* __restrict__ err = nullptr) {
-  __shared__ int sh[20 + 2 * (MAXT + 1)];
-  __shared__ int out[1024 * SCAN_SPT];          // one pass of exclusive offsets, stored coalesced
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x <= T) sh[20 + threadIdx.x] = 0;   // (K = 0: every segment start is 0)
-  if (threadIdx.x == 0) sh[17] = 0;
-  __syncthreads();
-  int carry = 0;
-  for (int64_t base = 0; base < K; base += 1024 * SCAN_SPT) {
-    const int64_t k0 = base + (int64_t)threadIdx.x * SCAN_SPT;
-    int v[SCAN_SPT];
-    if (k0 + SCAN_SPT <= K) {
-#pragma unroll
-      for (int j = 0; j < SCAN_SPT; j += 4) {
-        const int4 q = *reinterpret_cast<const int4*>(cnt + k0 + j);
-        v[j] = q.x; v[j + 1] = q.y; v[j + 2] = q.z; v[j + 3] = q.w;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < SCAN_SPT; ++j) v[j] = k0 + j < K ? cnt[k0 + j] : 0;
-    }
-    int local = 0;
-#pragma unroll
-    for (int j = 0; j < SCAN_SPT; ++j) local += v[j];
-    int x = local;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(x, off);
-      if (lane >= off) x += o;
-    }
-    if (lane == 63) sh[wave] = x;
-    __syncthreads();
-    if (wave == 0) {
-      const int wv = lane < 16 ? sh[lane] : 0;
-      int inc = wv;
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) {
-        const int o = __shfl_up(inc, off);
-        if (lane >= off) inc += o;
-      }
-      if (lane < 16) sh[lane] = inc - wv;
-      if (lane == 15) sh[16] = inc;
-    }
-    __syncthreads();
-    int run = carry + sh[wave] + x - local;
-#pragma unroll
-    for (int j = 0; j < SCAN_SPT; ++j) { out[threadIdx.x * SCAN_SPT + j] = run; run += v[j]; }
-    carry += sh[16];
-    __syncthreads();
-    const int64_t lim = K - base < 1024 * SCAN_SPT ? K - base : 1024 * SCAN_SPT;
-    for (int k = threadIdx.x; k < lim; k += 1024) seg[base + k] = out[k];
-    if (threadIdx.x < T) {                                  // seg[t * N] of this pass
-      const int64_t key = (int64_t)threadIdx.x * N;
-      if (key >= base && key < base + lim) sh[20 + threadIdx.x] = out[key - base];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    seg[K] = carry;
-    sh[20 + T] = carry;
-  }
-  if (flags) {
-    int f = 0;
-    for (int64_t i = threadIdx.x; i < nflags; i += 1024) f |= flags[i];
-    if (f) atomicOr(&sh[17], f);                             // (sh[17..19]: free after the scan)
-  }
-  __syncthreads();
-  if (flags && threadIdx.x < 4) err[threadIdx.x] = threadIdx.x ? 0 : (sh[17] | (carry != E_all ? 4 : 0));
-  type_split(sh + 20, carry, T, G, sh + 20 + MAXT + 1, wg_start);
-}
-
-// counts are consumed here: cnt[key] counts down, so edges land in a key's segment in arbitrary
-// order; mpn_segsort_kernel restores edge-id order inside each segment.
-__global__ __launch_bounds__(256) void mpn_scatter_kernel(const int64_t* __restrict__ ei, const int64_t* __restrict__ types,
-                                                          int64_t ts, int64_t N, int64_t E, int T, const int* __restrict__ seg,
-                                                          int* __restrict__ cnt, int* __restrict__ perm) {
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t s = ei[e], d = ei[E + e];
-    if (s < 0 || s >= N || d < 0 || d >= N) continue;
-    const int64_t t = T == 1 ? 0 : types[s * ts];
-    if (t < 0 || t >= T) continue;
-    const int64_t key = t * N + d;
-    perm[seg[key] + atomicSub(&cnt[key], 1) - 1] = (int)e;
-  }
-}
-
-// 16 lanes per (type, target) key: order the key's edges by original id (rank by counting).
-__global__ __launch_bounds__(256) void mpn_segsort_kernel(const int64_t* __restrict__ ei, int64_t E, int64_t K,
-                                                          const int* __restrict__ seg, const int* __restrict__ perm,
-                                                          int* __restrict__ s_src, int* __restrict__ s_dst,
-                                                          int* __restrict__ s_orig) {
-  const int sub = threadIdx.x & 15;
-  const int64_t key = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-  if (key >= K) return;
-  const int s0 = seg[key], n = seg[key + 1] - s0;
-  for (int a = sub; a < n; a += 16) {
-    const int v = perm[s0 + a];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) rank += perm[s0 + j] < v;
-    const int pos = s0 + rank;
-    s_orig[pos] = v;
-    s_src[pos] = (int)ei[v];
-    s_dst[pos] = (int)ei[E + v];
   }
 }
 
@@ -588,7 +290,7 @@ __device__ __forceinline__ void gemm_bf3(const __bf16* W, const bf16x8_t (&hi)[2
 // as bf16x3.
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-constexpr float F16_BIG = 16384.0f, F16_DOWN = 1.0f / 65536.0f, F16_UP = 65536.0f;
+constexpr float F16_BIG = 16384.0f, F16_DOWN = 1.0f / 65536.0f;
 template <int PREC>
 __host__ __device__ constexpr float dom() { return PREC == 2 ? 2048.0f : 1.0f; }
 template <int PREC>
@@ -610,11 +312,6 @@ __device__ __forceinline__ float frag_absmax(const float (&x)[4][4]) {
 #pragma unroll
   for (int b = 0; b < 4; ++b) m = fmaxf(m, fmaxf(fmaxf(fabsf(x[b][0]), fabsf(x[b][1])), fmaxf(fabsf(x[b][2]), fabsf(x[b][3]))));
   return m;
-}
-
-// wave-uniform: some |s x| of the fragment reaches 2^14 (or is NaN): take the range-scaled split
-__device__ __forceinline__ bool f16_big(const float (&x)[4][4], float s) {
-  return __any(!(frag_absmax(x) * s < F16_BIG));
 }
 
 // Range scale of one item (the lane column c = lane & 15; its 64 features sit in lanes c, c+16, c+32, c+48):
@@ -1267,8 +964,24 @@ __global__ __launch_bounds__(256) void embed_image_kernel(pemp_mlp emb, EmbedLay
 // floats of the composed image the kernel copies (no W1_e_cur tile)
 __host__ __device__ constexpr int embed_comp_floats(const EmbedLayout& Lo) { return (Lo.total + 3) & ~3; }
 
-__device__ inline void dma_to_lds(float* __restrict__ lds, const float* __restrict__ src, int n);
-__device__ __forceinline__ void lds_drain();
+// 16-byte LDS-DMA load per lane into the wave-contiguous LDS block at `l` (lane i -> l + 16 i bytes).
+// (A non-template function: hipcc drops the host stub of a kernel template that calls the builtin
+// directly.)
+__device__ __forceinline__ void dma16(const float* g, float* l) {
+  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+}
+
+// flat copy of `n` floats from global to LDS by LDS-DMA (copy_to_lds is the register form) (n multiple of 4, both ends 16-byte aligned): 1 KB per wave instruction,
+// the block's waves interleaved, nothing held in registers and nothing waited for here, so the loads
+// that follow overlap it; lds_drain() before the barrier that publishes it
+__device__ inline void dma_to_lds(float* __restrict__ lds, const float* __restrict__ src, int n) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int pieces = n >> 8, tail = n - (pieces << 8);
+  for (int k = wave; k < pieces; k += nw) dma16(src + 256 * k + 4 * lane, lds + 256 * k);
+  if (tail && wave == nw - 1 && 4 * lane < tail)
+    *reinterpret_cast<float4*>(&lds[256 * pieces + 4 * lane]) = ld4(src + 256 * pieces + 4 * lane);
+}
+__device__ __forceinline__ void lds_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // Edge embedding (sorted order), the fallback of the fused first pass: e_init = MLP(edge_attr[orig]),
 // Q0 = W1_e_init·e_init + b1 and R0 = Q0 + W1_e_cur·e_init (the first pass's layer-1 input).
@@ -1400,6 +1113,10 @@ struct EdgeStepArgs {
 // Diagnostic phase timestamps (-DPEMP_STAMPS builds only; tools/edge_timeline.py): lane 0 of each
 // wave stores s_memrealtime (100 MHz) into stamps[16 * global_wave + k].
 #ifdef PEMP_STAMPS
+// the edge pass `g_diag_stamp_pass` of every forward records the stamps (pemp_diag_stamps, after the kernels below;
+// launch_edge_step / launch_edge_first set EdgeStepArgs::stamps from the pass index they are given)
+static unsigned long long* g_diag_stamps = nullptr;
+static int g_diag_stamp_pass = 0;
 #define EDGE_STAMP(k)                                                                               \
   do {                                                                                              \
     if (a.stamps && lane == 0) {                                                                    \
@@ -1494,8 +1211,8 @@ __device__ __forceinline__ float seg_max(float v, int d) {
   return v;
 }
 
-// every lane of a chunk gets the value at the chunk tail (v non-decreasing along the chunk)
-__device__ __forceinline__ float seg_bcast_tail_max(float v, int u) {
+// every lane of a chunk gets the value at the chunk tail (v non-decreasing along the chunk); the PEMP_ASM_SCANS=0 path
+[[maybe_unused]] __device__ __forceinline__ float seg_bcast_tail_max(float v, int u) {
   float o;
   o = dppf<DPP_SHL1>(v, -INFINITY); v = fmaxf(v, u >= 1 ? o : -INFINITY);
   o = dppf<DPP_SHL2>(v, -INFINITY); v = fmaxf(v, u >= 2 ? o : -INFINITY);
@@ -1526,6 +1243,7 @@ __device__ __forceinline__ float readlane_f(float v, int l) {
 // lane, yet any instantiation that carried it outside that path (bf16x3) became timing-dependent across forwards, the
 // same with the DPP moved onto a v_mov_b32 and a plain fmac, and no cause was found. In the default
 // path it was worth <= 1 % of an edge pass (profiles/r06_asm_sums.md), so it was removed: no instantiation carries it.)
+#if PEMP_ASM_SCANS
 struct ChunkMasks {
   uint64_t f1, f2, f4, f8, b1, b2, b4, b8;   // lanes with d >= k (forward steps) / u >= k (backward steps)
 };
@@ -1551,7 +1269,7 @@ __device__ __forceinline__ float chunk_max_asm(float v, const ChunkMasks& mk) {
 #undef PEMP_MAXSTEP
   return v;
 }
-
+#endif
 
 
 // ---- edge-pass weight image --------------------------------------------------------------------
@@ -1748,13 +1466,6 @@ __device__ __forceinline__ void edge_ranges_role(const EdgeRangesArgs& a, int bx
 }
 
 __global__ __launch_bounds__(256) void edge_ranges_kernel(EdgeRangesArgs a) { edge_ranges_role(a, blockIdx.x); }
-
-// 16-byte LDS-DMA load per lane into the wave-contiguous LDS block at `l` (lane i -> l + 16 i bytes).
-// (A non-template function: hipcc drops the host stub of a kernel template that calls the builtin
-// directly.)
-__device__ __forceinline__ void dma16(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // LDS-DMA of the r rows of one 16-edge tile (sorted positions base .. base + 15; rows past the array
 // read 0, rows past the wave's range are loaded and ignored) into a 4 KB buffer: instruction i moves
@@ -2575,26 +2286,6 @@ __host__ __device__ inline int mlp_lds_floats(const pemp_mlp& m) {
   return n;
 }
 
-// all threads of the block: issue 8 float4 loads per thread, then 8 LDS stores
-__device__ __forceinline__ void stage_rows(float* __restrict__ lds, int ld, const float* __restrict__ src, int rows,
-                                           int cols) {
-  const int q = cols >> 2, total = rows * q;
-  for (int base = threadIdx.x; base < total; base += 8 * blockDim.x) {
-    float4 t[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t[k] = ld4(src + 4 * min(base + k * (int)blockDim.x, total - 1));
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int idx = base + k * (int)blockDim.x;
-      if (idx < total) {
-        const int r = idx / q, c4 = (idx - r * q) * 4;
-        *reinterpret_cast<float4*>(&lds[r * ld + c4]) = t[k];
-      }
-    }
-  }
-}
-
 // Stage up to three MLPs back to back (the layout mlp_lds_frag / mlp_lds_floats assume) with ONE
 // batched pass: every thread issues 8 float4 loads before its first LDS store, over the
 // concatenation of all weight and bias segments (weights row-major [16 OB][16 KB], biases one row).
@@ -2636,11 +2327,6 @@ __device__ inline void plan_element(const StagePlan& p, int idx, const float** s
   *dst = d0 + r * ld + 4 * (local - r * q);
 }
 
-// First kernel of a forward: zero the counters.
-__global__ __launch_bounds__(256) void zero_words_kernel(int* __restrict__ p, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0;
-}
-
 // LDS image of the node-side MLPs ([emb | node head | class head], mlp_lds_floats layouts): built once
 // per weight set (pemp_mpn_node_image) or, without one, once per forward into the workspace
 __global__ __launch_bounds__(256) void stage_image_kernel(StagePlan plan, float* __restrict__ img) {
@@ -2667,17 +2353,6 @@ __device__ inline void copy_to_lds(float* __restrict__ lds, const float* __restr
   }
 }
 
-// the same copy by LDS-DMA (n multiple of 4, both ends 16-byte aligned): 1 KB per wave instruction,
-// the block's waves interleaved, nothing held in registers and nothing waited for here, so the loads
-// that follow overlap it; lds_drain() before the barrier that publishes it
-__device__ inline void dma_to_lds(float* __restrict__ lds, const float* __restrict__ src, int n) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const int pieces = n >> 8, tail = n - (pieces << 8);
-  for (int k = wave; k < pieces; k += nw) dma16(src + 256 * k + 4 * lane, lds + 256 * k);
-  if (tail && wave == nw - 1 && 4 * lane < tail)
-    *reinterpret_cast<float4*>(&lds[256 * pieces + 4 * lane]) = ld4(src + 256 * pieces + 4 * lane);
-}
-__device__ __forceinline__ void lds_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // whole staged MLP on one wave's fragments (widths <= 64); result in `a`
 __device__ inline void mlp_lds_frag(const float* lds, const pemp_mlp& m, float (&a)[4][4]) {
@@ -3089,11 +2764,6 @@ __global__ __launch_bounds__(256) void prelude_b_kernel(EdgeRangesArgs ra, NodeT
   else node_table_role<PREC, TBL_TILES, false>(ta, xs, bx - split);
 }
 
-static int grid1d(int64_t total, int block, int cap = 65536) {
-  int64_t g = (total + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 static bool published_head(const pemp_mlp& m) {
   return m.n_layers == 3 && m.layer[0].in_dim == 64 && m.layer[0].out_dim == 64 && m.layer[0].relu &&
          m.layer[1].in_dim == 64 && m.layer[1].out_dim == 32 && m.layer[1].relu && m.layer[2].in_dim == 32 &&
@@ -3121,8 +2791,13 @@ static void launch_edge_step_p(const EdgeStepArgs& a, bool head, bool pub, int g
   else launch_edge_step_s<AGG, PREC, UPD, STAGE_LAST>(a, head, pub, grid, st);
 }
 
-static bool edge_upd_fused(const pemp_mpn_desc& d, const pemp_mpn_weights& w);
-static bool edge_pub_head(const pemp_mpn_desc& d, const pemp_mpn_weights& w);
+// whether the edge passes pre-apply the update block (UPD) and carry the published head (HEAD 1)
+static bool edge_upd_fused(const pemp_mpn_desc& d, const pemp_mpn_weights& w) {
+  return (d.aggr == PEMP_AGGR_ATTN || d.aggr == PEMP_AGGR_MEAN) && w.upd_w && (d.precision == PEMP_PREC_FP32 || w.upd_bf);
+}
+static bool edge_pub_head(const pemp_mpn_desc& d, const pemp_mpn_weights& w) {
+  return published_head(w.edge_head) && (d.precision == PEMP_PREC_FP32 || w.head_bf);
+}
 // the edge embedding's arithmetic (ForwardPlan::emb_prec) and where its LDS image follows the passes' image
 static int embed_prec(const pemp_mpn_desc& d, const pemp_mpn_weights& w) {
   return d.precision != PEMP_PREC_FP32 && w.emb_bf ? d.precision : PEMP_PREC_FP32;
@@ -3145,14 +2820,6 @@ static EdgeImgArgs edge_image_args(const pemp_mpn_desc& d, const pemp_mpn_weight
   return a;
 }
 
-// whether the edge passes pre-apply the update block (UPD) and carry the published head (HEAD 1)
-static bool edge_upd_fused(const pemp_mpn_desc& d, const pemp_mpn_weights& w) {
-  return (d.aggr == PEMP_AGGR_ATTN || d.aggr == PEMP_AGGR_MEAN) && w.upd_w && (d.precision == PEMP_PREC_FP32 || w.upd_bf);
-}
-static bool edge_pub_head(const pemp_mpn_desc& d, const pemp_mpn_weights& w) {
-  return published_head(w.edge_head) && (d.precision == PEMP_PREC_FP32 || w.head_bf);
-}
-
 // The one dispatch from a run-time PEMP_PREC_* to a template argument: f(std::integral_constant<int, PREC>{}).
 template <class F>
 static void with_prec(int prec, F&& f) {
@@ -3162,14 +2829,33 @@ static void with_prec(int prec, F&& f) {
 }
 
 // UPD is instantiated for the linear aggregations only (U · max(m) != max(U · m))
+// -DPEMP_STAMPS builds: the pass chosen through pemp_diag_stamps records its phase stamps
+static void set_stamps(EdgeStepArgs& a, int pass) {
+#ifdef PEMP_STAMPS
+  a.stamps = pass == g_diag_stamp_pass ? g_diag_stamps : nullptr;
+#else
+  (void)a;
+  (void)pass;
+#endif
+}
+
+// `pass`: the iteration (for the phase stamps)
 template <int AGG>
-static void launch_edge_step(const EdgeStepArgs& a, bool head, bool pub, int grid, int prec, bool upd, int stage,
+static void launch_edge_step(EdgeStepArgs a, int pass, bool head, bool pub, int grid, int prec, bool upd, int stage,
                              hipStream_t st) {
+  set_stamps(a, pass);
   constexpr int U = AGG == PEMP_AGGR_ATTN || AGG == PEMP_AGGR_MEAN ? 1 : 0;
   with_prec(prec, [&](auto P) {
     if (U && upd) launch_edge_step_p<AGG, decltype(P)::value, U>(a, head, pub, grid, stage, st);
     else launch_edge_step_p<AGG, decltype(P)::value, 0>(a, head, pub, grid, stage, st);
   });
+}
+
+// embedding + pass 0 in one launch (edge_step_kernel STAGE_FIRST)
+static void launch_edge_first(EdgeStepArgs a, int pass, int grid, hipStream_t st) {
+  set_stamps(a, pass);
+  hipLaunchKernelGGL((edge_step_kernel<PEMP_AGGR_ATTN, 0, 2, 1, STAGE_MID | STAGE_FIRST>), dim3(grid),
+                     dim3(64 * EDGE_WAVES), 0, st, a);
 }
 
 static int rows_mlp(const char* label, const pemp_mlp& m, const float* in, int64_t ld_in, int64_t M, float* out,
@@ -3209,164 +2895,6 @@ static StagePlan node_image_plan(const pemp_mpn_weights& w) {
                     heads ? &w.class_head : nullptr);
 }
 
-// type-major order of the edges (the first five kernels of a forward; pemp_mpn_prepare)
-// ---- prepare for a fully-connected batch (pemp_mpn_forward_fully) -----------------------------
-// For the graph constructor's fully graph (every ordered pair i != j of an image, edge id
-// eoff_b + i (n_b - 1) + (j < i ? j : j - 1), ConstructGraph.py:376-381) the type-major order is
-// known in closed form, so the four sorting kernels collapse into one: segment (t, d) holds the
-// type-t nodes of d's image except d, in index order, and starts at
-//   seg(t, d) = sum_{t' < t} E_t' + sum_{b' < b} n_{b',t} (n_b' - 1) + d_local n_{b,t} - #{type-t nodes before d}
-// with E_t = sum_b n_{b,t} (n_b - 1). Identical arrays to launch_prepare's (tested bit for bit).
-constexpr int FULLY_MAXB = 64;      // images per batch
-constexpr int FULLY_MAXN = 2048;    // nodes per image (LDS lists)
-constexpr int FULLY_PARTS = 4;   // threads per (type, target) segment in fully_prepare_kernel
-struct FullyPrepArgs {
-  const int64_t* node_off;          // [B + 1] device
-  int B;
-  const int64_t* types;
-  int64_t ts, N;
-  int T, Gsplit;
-  int *seg, *wg_start, *s_src, *s_dst, *s_orig, *err;
-  const int64_t* ne;   // capacity mode: device-side (N, E, overflow); an overflowed batch prepares as empty images
-};
-
-// the LDS of one fully_prepare workgroup
-struct FullyPrepLds {
-  long long et_sh[MAXT], cb_sh[MAXT];
-  long long eoff_sh;
-  int cnt_bt[FULLY_MAXB][MAXT];
-  int tbase[MAXT + 1];        // sum_{t' < t} E_t' (fits int: E < 2^31)
-  int noff[FULLY_MAXB + 1];
-  int sorted[FULLY_MAXN], lty[FULLY_MAXN];
-  int tstart_l[MAXT + 1], gt_sh[MAXT];
-  int bad_sh;
-};
-
-// block (bx of gx, image by) over its LDS (the body of fully_prepare_kernel, and a role of prelude_a_kernel)
-__device__ __forceinline__ void fully_prepare_role(const FullyPrepArgs& a, FullyPrepLds& s, int bx, int by, int gx) {
-  auto& cnt_bt = s.cnt_bt;
-  auto& et_sh = s.et_sh;
-  auto& cb_sh = s.cb_sh;
-  auto& tbase = s.tbase;
-  auto& noff = s.noff;
-  auto& sorted = s.sorted;
-  auto& lty = s.lty;
-  auto& tstart_l = s.tstart_l;
-  auto& gt_sh = s.gt_sh;
-  int& bad_sh = s.bad_sh;
-  long long& eoff_sh = s.eoff_sh;
-  const int b = by, T = a.T, B = a.B;
-  const int64_t N = a.ne ? a.ne[0] : a.N;
-  const bool empty = a.ne && a.ne[2];   // capacity overflow: node_off was not written
-  for (int i = threadIdx.x; i <= B; i += 256) noff[i] = empty ? 0 : (int)a.node_off[i];
-  for (int i = threadIdx.x; i < FULLY_MAXB * MAXT; i += 256) (&cnt_bt[0][0])[i] = 0;
-  if (threadIdx.x == 0) bad_sh = 0;
-  __syncthreads();
-  // per-(image, type) node counts of the whole batch (every block: N is a few thousand at most); a thread's type
-  // loads go out 8 at a time, ahead of the searches and the LDS counts that use them
-  for (int64_t n0 = threadIdx.x; n0 < N; n0 += 256 * 8) {
-    int64_t tv[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int64_t n = n0 + 256 * k;
-      tv[k] = n < N ? a.types[n * a.ts] : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int64_t n = n0 + 256 * k;
-      if (n >= N) break;
-      int lo = 0, hi = B - 1;
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (noff[mid] <= n) lo = mid; else hi = mid - 1;
-      }
-      const int64_t t = T == 1 ? 0 : tv[k];          // one message MLP ignores the types, like mpn_count_kernel
-      if (t >= 0 && t < T) atomicAdd(&cnt_bt[lo][t], 1);
-      else bad_sh = 1;                               // skipped as a source, like mpn_count_kernel
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < T) {
-    const int t = threadIdx.x;
-    long long e = 0, cb = 0;
-    for (int bb = 0; bb < B; ++bb) {
-      const int nb = noff[bb + 1] - noff[bb];
-      const long long v = (long long)cnt_bt[bb][t] * (nb > 0 ? nb - 1 : 0);
-      if (bb < b) cb += v;
-      e += v;
-    }
-    et_sh[t] = e;
-    cb_sh[t] = cb;
-  }
-  const int ob = noff[b], nb = noff[b + 1] - noff[b];
-  for (int i = threadIdx.x; i < nb; i += 256) {
-    const int64_t t = T == 1 ? 0 : a.types[(int64_t)(ob + i) * a.ts];
-    lty[i] = (t >= 0 && t < T) ? (int)t : -1;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int acc = 0;
-    for (int t = 0; t < T; ++t) { tbase[t] = acc; acc += (int)et_sh[t]; }
-    tbase[T] = acc;
-    acc = 0;
-    for (int t = 0; t < T; ++t) { tstart_l[t] = acc; acc += cnt_bt[b][t]; }
-    tstart_l[T] = acc;
-    long long eo = 0;
-    for (int bb = 0; bb < b; ++bb) { const long long m = noff[bb + 1] - noff[bb]; eo += m * (m > 0 ? m - 1 : 0); }
-    eoff_sh = eo;
-  }
-  __syncthreads();
-  // the image's nodes grouped by type, index order kept (rank = same-type nodes before i)
-  for (int i = threadIdx.x; i < nb; i += 256) {
-    const int t = lty[i];
-    if (t < 0) continue;
-    int r = 0;
-    for (int j = 0; j < i; ++j) r += lty[j] == t;
-    sorted[tstart_l[t] + r] = i;
-  }
-  __syncthreads();
-  // segments (t, d): one thread each
-  const long long eoff = eoff_sh;
-  // FULLY_PARTS consecutive threads per segment, entry m of the segment on thread (m - s0) % FULLY_PARTS: its slot is
-  // the segment start + its rank, one less past d when d itself is of type t (d is left out)
-  for (int q = bx * 256 + threadIdx.x; q < T * nb * FULLY_PARTS; q += gx * 256) {
-    const int sq = q / FULLY_PARTS, part = q - sq * FULLY_PARTS;
-    const int t = sq / nb, dl = sq - t * nb;
-    const int s0 = tstart_l[t], s1 = tstart_l[t + 1];
-    int lo = s0, hi = s1;                              // type-t nodes before dl
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (sorted[mid] < dl) lo = mid + 1; else hi = mid;
-    }
-    const int before = lo - s0;
-    const int64_t d = ob + dl;
-    const int pos = tbase[t] + (int)cb_sh[t] + dl * (s1 - s0) - before;
-    const bool d_in = lty[dl] == t;
-    if (part == 0) a.seg[(int64_t)t * N + d] = pos;
-    for (int m = s0 + part; m < s1; m += FULLY_PARTS) {   // the segment: type-t nodes except d, in order
-      const int i = sorted[m];
-      if (i == dl) continue;
-      const int p = pos + (m - s0) - (d_in && i > dl ? 1 : 0);
-      a.s_src[p] = ob + i;
-      a.s_dst[p] = (int)d;
-      a.s_orig[p] = (int)(eoff + (long long)i * (nb - 1) + (dl < i ? dl : dl - 1));
-    }
-  }
-  if (bx == 0 && by == 0) {
-    if (threadIdx.x == 0) {
-      a.seg[(int64_t)T * N] = tbase[T];
-      a.err[0] = bad_sh ? 2 : 0;
-      a.err[1] = a.err[2] = a.err[3] = 0;
-    }
-    type_split(tbase, tbase[T], T, a.Gsplit, gt_sh, a.wg_start);
-  }
-}
-
-__global__ __launch_bounds__(256) void fully_prepare_kernel(FullyPrepArgs a) {
-  __shared__ FullyPrepLds s;
-  fully_prepare_role(a, s, blockIdx.x, blockIdx.y, gridDim.x);
-}
-
 // Launch A of the paired prelude (Forward::prelude): the closed-form edge order (blocks [0, split): block x of gx
 // of image y at y gx + x, fully_prepare_role) beside the node embedding (blocks [split, gridDim.x): one 16-node tile
 // each, node_rows_role in ROWS_EMBED mode). Both read the call's inputs and what earlier launches wrote, nothing of
@@ -3383,551 +2911,19 @@ static size_t prelude_a_lds_bytes(const NodeRowsArgs& na) {
   return std::max(node_rows_lds_bytes(na), sizeof(FullyPrepLds));
 }
 
-// ---- Symmetric prepare: edge_index sorted by (src, dst) without duplicates and symmetric (PyG to_undirected's
-// coalesced output: knn_mpn_graph, feature_knn_mpn_graph, score_based_graph, ConstructGraph.py:363-422).
-// The incoming edges of d are then the entries of row d read backwards: segment (t, d) = the type-t entries of
-// row d in ascending source order (= edge-id order, the sorting prepare's tie order), and the id of the incoming
-// edge (x -> d) is the position of d in row x. Three launches, no zeroing, no atomics on the data path:
-//   sym_rows_kernel   one wave per node n: row n's bounds (64-way probes + one coalesced run), its entries packed
-//                     as (dst | type(dst) << 24), the (type, n) counts written directly (all T of them), checks;
-//   mpn_scan_kernel   (shared with the sorting prepare) + the reduction of the per-node check flags;
-//   sym_place_kernel  one wave per node d: each entry's rank among the same-type entries before it (ballots),
-//                     its segment slot, and the incoming edge's id by a binary search of d in row x.
-// Measured alternatives: per-image blocks over LDS adjacency bit rows (8 busy CUs) 31-35 us; a per-edge walk along
-// row d (knn rows hold ~60 entries) 25 us for the placement alone; the sorting prepare 25 us (C3 knn).
-constexpr int SYM_TBITS = 24;        // packed row entry: dst (< 2^24) | type << 24 (type 31: invalid, never matched)
-constexpr unsigned SYM_NMASK = (1u << SYM_TBITS) - 1u;
-
-// first position p in [0, n) with a[p] >= key (n if none), by one wave: 64-way probes per round (E = 250k:
-// 3 rounds of one load per lane, no barriers); bounded on an unsorted list too
-__device__ int64_t wave_lower_bound(const int64_t* __restrict__ a, int64_t n, int64_t key) {
-  const int lane = threadIdx.x & 63;
-  int64_t lo = 0, hi = n;                          // a[< lo] < key <= a[>= hi]
-  while (lo < hi) {                                // (uniform)
-    const int64_t s = (hi - lo + 63) / 64;
-    const int64_t q = lo + (int64_t)lane * s;
-    const unsigned long long m = __ballot(q < hi && a[q] < key);
-    const int c = __popcll(m);                     // probes below key form a prefix
-    if (c == 0) break;                             // a[lo] >= key
-    const int64_t nlo = lo + (int64_t)(c - 1) * s + 1, nhi = min(hi, lo + (int64_t)c * s);
-    lo = nlo;
-    hi = nhi;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(256) void sym_rows_kernel(const int64_t* __restrict__ ei, const int64_t* __restrict__ types,
-                                                       int64_t ts, int64_t N, int64_t E, int T, int* __restrict__ cnt,
-                                                       int2* __restrict__ rows, unsigned* __restrict__ packed,
-                                                       int* __restrict__ flags) {
-  const int lane = threadIdx.x & 63;
-  const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (n >= N) return;                                         // (wave-uniform)
-  const int64_t r0 = wave_lower_bound(ei, E, n);              // row n starts here if the list is sorted
-  int f = 0, tcount = 0;                                      // lane t < T: type-t entries of row n
-  int64_t r = r0, prev = -1;
-  for (;;) {                                                  // the run of source n, 64 entries per round
-    const int64_t e = r + lane;
-    const bool in = e < E && ei[e] == n;
-    const unsigned long long out = __ballot(!in);
-    const int len = out ? __builtin_ctzll(out) : 64;          // (entries past a mismatch are not the row's)
-    const bool mine = lane < len;
-    const int64_t d = mine ? ei[E + e] : 0;
-    int t = 31;
-    if (mine) {
-      if (d < 0 || d >= N) f |= 1;
-      else {
-        const int64_t tt = T == 1 ? 0 : types[d * ts];
-        if (tt >= 0 && tt < T) t = (int)tt;
-        else f |= 2;                                          // (d is a source too: the list is symmetric)
-      }
-      packed[e] = (unsigned)d | ((unsigned)t << SYM_TBITS);
-    }
-    const int64_t dp = __shfl_up(d, 1);
-    if (mine && (lane ? dp : prev) >= d) f |= 4;              // targets of a row strictly ascending
-    unsigned long long rem = __ballot(mine && t < T);
-    while (rem) {                                             // one round per distinct type in the chunk
-      const int tu = __shfl(t, __builtin_ctzll(rem));
-      const unsigned long long m = __ballot(mine && t == tu);
-      if (lane == tu) tcount += __popcll(m);
-      rem &= ~m;
-    }
-    prev = __shfl(d, 63);
-    r += len;
-    if (len < 64) break;
-  }
-  if ((r0 > 0 && ei[r0 - 1] >= n) || (r < E && ei[r] < n)) f |= 4;   // neighbouring runs: ascending sources
-  if (lane < T) cnt[(int64_t)lane * N + n] = tcount;
-  for (int o = 32; o; o >>= 1) f |= __shfl_xor(f, o);
-  if (lane == 0) {
-    rows[n] = make_int2((int)r0, (int)r);
-    flags[n] = f;
-  }
-}
-
-__global__ __launch_bounds__(256) void sym_place_kernel(int64_t N, int T, const int* __restrict__ seg,
-                                                        const int2* __restrict__ rows,
-                                                        const unsigned* __restrict__ packed, int* __restrict__ s_src,
-                                                        int* __restrict__ s_dst, int* __restrict__ s_orig,
-                                                        int* __restrict__ err) {
-  const int lane = threadIdx.x & 63;
-  const int64_t d = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (d >= N) return;                                         // (wave-uniform)
-  const int2 rb = rows[d];
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int carry = 0, bad = 0;                                     // lane t: type-t entries of row d in earlier chunks
-  for (int c = rb.x; c < rb.y; c += 64) {
-    const int e = c + lane;
-    const bool mine = e < rb.y;
-    const unsigned w = mine ? packed[e] : 0u;
-    const int x = (int)(w & SYM_NMASK), t = (int)(w >> SYM_TBITS);
-    const bool ok = mine && t < T;
-    int rank = 0;
-    unsigned long long rem = __ballot(ok);
-    while (rem) {
-      const int tu = __shfl(t, __builtin_ctzll(rem));
-      const unsigned long long m = __ballot(ok && t == tu);
-      const int cu = __shfl(carry, tu);
-      if (ok && t == tu) rank = cu + __popcll(m & below);
-      if (lane == tu) carry += __popcll(m);
-      rem &= ~m;
-    }
-    if (ok) {
-      const int pos = seg[(int64_t)t * N + d] + rank;
-      const int2 rx = rows[x];                                // row x holds d if the list is symmetric
-      int lo = rx.x, hi = rx.y;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if ((int)(packed[mid] & SYM_NMASK) < (int)d) lo = mid + 1; else hi = mid;
-      }
-      const bool found = lo < rx.y && (int)(packed[lo] & SYM_NMASK) == (int)d;
-      bad |= !found;
-      s_src[pos] = x;
-      s_dst[pos] = (int)d;
-      s_orig[pos] = found ? lo : 0;
-    }
-  }
-  if (__ballot(bad) && lane == 0) atomicOr(err, 8);          // (x -> d) missing: not symmetric
-}
-
-// Symmetric prepare, step 2 (instead of the one-block mpn_scan): one 1024-thread block per source type t. The
-// segment starts are seg[t N + d] = base_t + sum_{d' < d} cnt[t, d'] with base_t = the edges of all types before
-// t: every block sums every type's counts (one wave per type, T N ints, L2-resident) and scans its own type's N
-// counts, so the T scans run side by side instead of one block walking all T N counts. The last block also writes
-// seg[T N], the edge passes' type split (wg_start) and the contract flags (err[0..3]), as mpn_scan does.
-__global__ __launch_bounds__(1024) void sym_scan_kernel(const int* __restrict__ cnt, int64_t N, int T, int G,
-                                                        int* __restrict__ seg, int* __restrict__ wg_start,
-                                                        const int* __restrict__ flags, int64_t E_all,
-                                                        int* __restrict__ err) {
-  __shared__ int tb[MAXT + 1], gt[MAXT + 1], wsum[16], sh[4];
-  __shared__ int out[1024 * SCAN_SPT];
-  const int t = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool last = t == T - 1;
-  if (threadIdx.x < 4) sh[threadIdx.x] = 0;
-  // every type's total, one wave per type (wave w: types w, w + 16), all of a wave's loads in flight together
-  for (int tt = wave; tt < T; tt += 16) {
-    int v = 0;
-    const int* ct = cnt + (int64_t)tt * N;
-#pragma unroll 8
-    for (int64_t n = lane; n < N; n += 64) v += ct[n];
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    if (lane == 0) tb[tt] = v;
-  }
-  if (last) {                                          // the contract flags of every node (sym_rows_kernel)
-    int f = 0;
-    for (int64_t i = threadIdx.x; i < N; i += 1024) f |= flags[i];
-    if (f) atomicOr(&sh[0], f);
-  }
-  __syncthreads();
-  int base = 0;
-  for (int tt = 0; tt < t; ++tt) base += tb[tt];
-  // this type's segment starts: passes of 1024 x SCAN_SPT counts, carry across passes
-  int carry = base;
-  const int* c = cnt + (int64_t)t * N;
-  for (int64_t b0 = 0; b0 < N; b0 += 1024 * SCAN_SPT) {
-    const int64_t k0 = b0 + (int64_t)threadIdx.x * SCAN_SPT;
-    int v[SCAN_SPT];
-#pragma unroll
-    for (int j = 0; j < SCAN_SPT; ++j) v[j] = k0 + j < N ? c[k0 + j] : 0;
-    int local = 0;
-#pragma unroll
-    for (int j = 0; j < SCAN_SPT; ++j) local += v[j];
-    int x = local;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(x, off);
-      if (lane >= off) x += o;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w2 = 0; w2 < 16; ++w2) {
-      before += w2 < wave ? wsum[w2] : 0;
-      all += wsum[w2];
-    }
-    int run = carry + before + x - local;
-#pragma unroll
-    for (int j = 0; j < SCAN_SPT; ++j) { out[threadIdx.x * SCAN_SPT + j] = run; run += v[j]; }
-    carry += all;
-    __syncthreads();
-    const int64_t lim = N - b0 < 1024 * SCAN_SPT ? N - b0 : 1024 * SCAN_SPT;
-    for (int64_t k = threadIdx.x; k < lim; k += 1024) seg[(int64_t)t * N + b0 + k] = out[k];
-    __syncthreads();
-  }
-  if (!last) return;                                   // (block-uniform)
-  if (threadIdx.x == 0) {                              // type starts for the split; the total closes seg
-    int acc = 0;
-    for (int tt = 0; tt < T; ++tt) {
-      const int v = tb[tt];
-      tb[tt] = acc;
-      acc += v;
-    }
-    tb[T] = acc;
-    seg[(int64_t)T * N] = acc;
-    sh[1] = acc;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) err[threadIdx.x] = threadIdx.x ? 0 : (sh[0] | (sh[1] != E_all ? 4 : 0));
-  type_split(tb, sh[1], T, G, gt, wg_start);
-}
-
-// ---- knn prepare (pemp_mpn_forward_knn): the graph constructor's knn graph (knn_mpn_graph / feature_knn_mpn_graph,
-// ConstructGraph.py:363-374) handed over as the bit rows its build emitted the edges from (graph.hip,
-// knn_rows_kernel / knn_emit_rows_kernel): row n = bit mask R[n][w] over the image-local nodes 64 w + j, the edge
-// (n -> m) has id ebase_b + rowstart[n] + #{bits of row n below m}, and R is symmetric (A | A^T). Then
-//   cnt(t, d)  = sum_w popcount(R[d][w] & M_t[b][w])     (M_t: the type-t nodes of d's image as bit words),
-//   E_t        = sum over type-t nodes x of popcount(R[x]) (symmetry: the type-t sources of every row),
-//   the (x -> d) id is a popcount of row x below d (no search),
-// so the three launches of the symmetric prepare (rows with their binary searches, the scan, the placement)
-// collapse into one: blocks (t, chunk of KP_CH rows) each count and scan all N rows for type t in LDS (one round
-// of row loads, the type masks from the rows' own types) and place their chunk's sources through an LDS list,
-// entry-parallel (a second round of loads: one word of each source row and its start). The same arrays as
-// launch_prepare_sym's (tested bit for bit).
-#ifndef PEMP_KP_CLOCKS
-#define PEMP_KP_CLOCKS 0
-#endif
-constexpr int KP_MAXB = 64, KP_MAXN = 4096, KP_W = 8;   // images, nodes per batch, bit words per row (512 nodes)
-constexpr int KP_LIST = 12288;                          // sources one block lists in LDS (else placed row by row)
-constexpr int KP_CH = 256;                              // rows placed per block (a divisor of 1024)
-
-struct KnnPrepArgs {
-  const unsigned long long* R;   // [N][KP_W]
-  const int* rowstart;           // [N] row start inside its image
-  const int64_t* node_off;       // [B + 1]
-  const int64_t* ecount;         // [B] edges per image
-  int B;
-  const int64_t* types;
-  int64_t ts, N, E;
-  int T, G;
-  int *seg, *wg_start, *s_src, *s_dst, *s_orig, *err;
-  int list_cap;                  // <= KP_LIST (PEMP_KNN_LIST_CAP: the row-by-row placement in tests)
-};
-
-__device__ __forceinline__ int kp_image(const int* noff, int B, int d) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (noff[mid] <= d) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(1024) void knn_prepare_kernel(KnnPrepArgs a) {
-  __shared__ unsigned long long M[KP_MAXB * KP_W];   // bit j of word (b, w): node 64 w + j of image b has type t
-  __shared__ int noff[KP_MAXB + 1], ebase[KP_MAXB + 1];
-  __shared__ int tot[MAXT + 1], tst[MAXT + 1], gt[MAXT], wsum[16];
-  __shared__ int bad_sh;
-  __shared__ int cs[KP_MAXN];                        // cnt(t, d), then the segment starts
-  __shared__ unsigned short pw[KP_MAXN][KP_W];       // entries of row n in its words before w
-  __shared__ int lst[KP_LIST];                       // the chunk's sources in segment order: x << 10 | (d - d0)
-  __shared__ int cend;
-  constexpr int SPT = KP_MAXN / 1024;
-  const int t = blockIdx.x, T = a.T, B = a.B, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int N = (int)a.N;
-#if PEMP_KP_CLOCKS   // diagnostics: per-phase wall clock (100 MHz) of two blocks, printed
-  long long clk[6];
-  clk[0] = wall_clock64();
-#define KP_CLK(i) clk[i] = wall_clock64()
-#else
-#define KP_CLK(i) (void)0
-#endif
-  // the offsets first (the in-order load counter: the barrier below then waits for them, not for the rows), then
-  // the words and types of this thread's first two rows (words past a row's image are masked below: R is [N][KP_W])
-  // (clamped indices, no branches: straight-line loads let the barrier wait count exactly)
-  const int no = (int)a.node_off[min(tid, B)];
-  const int ec = (int)a.ecount[min(lane, B - 1)];
-  __builtin_amdgcn_sched_barrier(0);                 // (keeps the offsets' loads ahead of the rows')
-  unsigned long long rr[2][KP_W];
-  int64_t tr[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int d = min(tid + 1024 * i, N - 1);        // (rows past N are loaded but never used)
-#pragma unroll
-    for (int w = 0; w < KP_W; ++w) rr[i][w] = a.R[(int64_t)d * KP_W + w];
-    tr[i] = a.types[(int64_t)d * a.ts];
-  }
-  if (T == 1) tr[0] = tr[1] = 0;                     // one message MLP ignores the types, like mpn_count_kernel
-  if (tid <= B) noff[tid] = no;
-  if (wave == 1) {                                   // edge id base of every image (B <= 64)
-    const int e = lane < B ? ec : 0;
-    int x = e;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(x, o);
-      if (lane >= o) x += v;
-    }
-    if (lane < B) ebase[lane] = x - e;
-    if (lane == B - 1) ebase[B] = x;
-  }
-  if (tid <= MAXT) tot[tid] = 0;
-  if (tid == 0) bad_sh = 0;
-  for (int q = tid; q < B * KP_W; q += 1024) M[q] = 0ull;
-  __syncthreads();
-  KP_CLK(1);
-  // type-t masks of every image word, from the rows' own types (no second round of loads)
-  bool bad = false;
-  auto mark = [&](int d, int64_t tt) {
-    if (tt < 0 || tt >= T) bad = true;               // skipped as a source, like mpn_count_kernel
-    if (tt == t) {
-      const int b = kp_image(noff, B, d), dl = d - noff[b];
-      atomicOr(&M[b * KP_W + (dl >> 6)], 1ull << (dl & 63));
-    }
-  };
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-    if (tid + 1024 * i < N) mark(tid + 1024 * i, tr[i]);
-  for (int d = tid + 2048; d < N; d += 1024) mark(d, T == 1 ? 0 : a.types[(int64_t)d * a.ts]);
-  if (__ballot(bad) && lane == 0) bad_sh = 1;
-  __syncthreads();
-  KP_CLK(2);
-  // every row: cnt(t, d), its word prefix counts and its degree (the per-type edge totals)
-  auto row = [&](int d, const unsigned long long* v, int64_t tt) {
-    const int b = kp_image(noff, B, d), nb = noff[b + 1] - noff[b], wpr = (nb + 63) >> 6;
-    int c = 0, deg = 0;
-#pragma unroll
-    for (int w = 0; w < KP_W; ++w) {
-      pw[d][w] = (unsigned short)deg;
-      if (w < wpr) {
-        c += __popcll(v[w] & M[b * KP_W + w]);
-        deg += __popcll(v[w]);
-      }
-    }
-    cs[d] = c;
-    if (tt >= 0 && tt < T) atomicAdd(&tot[tt], deg);
-  };
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-    if (tid + 1024 * i < N) row(tid + 1024 * i, rr[i], tr[i]);
-  for (int d = tid + 2048; d < N; d += 1024) {
-    unsigned long long v[KP_W];
-#pragma unroll
-    for (int w = 0; w < KP_W; ++w) v[w] = a.R[(int64_t)d * KP_W + w];
-    row(d, v, T == 1 ? 0 : a.types[(int64_t)d * a.ts]);
-  }
-  __syncthreads();
-  KP_CLK(3);
-  int base = 0;
-  for (int u = 0; u < t; ++u) base += tot[u];
-  const int d0 = blockIdx.y * KP_CH, d1 = min(N, d0 + KP_CH);   // this block's rows (placement, seg)
-  {                                                  // exclusive scan of cs in place (SPT counts per thread)
-    int v[SPT], local = 0;
-#pragma unroll
-    for (int j = 0; j < SPT; ++j) {
-      const int d = tid * SPT + j;
-      v[j] = d < N ? cs[d] : 0;
-      local += v[j];
-    }
-    int x = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(x, o);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int run = base + x - local;
-    for (int w2 = 0; w2 < wave; ++w2) run += wsum[w2];
-#pragma unroll
-    for (int j = 0; j < SPT; ++j) {
-      const int d = tid * SPT + j;
-      if (d < N) cs[d] = run;
-      if (d >= d0 && d < d1) a.seg[(int64_t)t * N + d] = run;
-      run += v[j];
-    }
-    if (tid == 1023) cend = run;                     // the end of type t's segments
-  }
-  __syncthreads();
-  KP_CLK(4);
-  // placement: the type-t sources x of row d in ascending order; the (x -> d) id = the image's base + row x's
-  // start + its entries before d (word prefix from LDS + one word of row x). The chunk's positions are contiguous
-  // ([p0, p1)): each row lists its sources in LDS, then the list is placed entry-parallel (coalesced stores).
-  const int p0 = d0 < d1 ? cs[d0] : 0, p1 = d1 < N ? cs[d1] : cend;
-  if (p1 - p0 <= a.list_cap) {                       // (block-uniform)
-    // row d is listed by the thread that loaded it (d = tid + 1024 i, rr[i])
-    const int dr = (d0 & ~1023) + tid, ir = d0 >> 10;
-    if (dr >= d0 && dr < d1) {
-      const int b = kp_image(noff, B, dr), ob = noff[b], nb = noff[b + 1] - ob, wpr = (nb + 63) >> 6;
-      int q = cs[dr] - p0;
-#pragma unroll
-      for (int w = 0; w < KP_W; ++w) {               // (static word indices: rr stays in registers)
-        if (w >= wpr) break;
-        unsigned long long r = ir == 0 ? rr[0][w] : ir == 1 ? rr[1][w] : a.R[(int64_t)dr * KP_W + w];
-        r &= M[b * KP_W + w];
-        while (r) {
-          lst[q++] = (ob + 64 * w + __builtin_ctzll(r)) << 10 | (dr - d0);
-          r &= r - 1ull;
-        }
-      }
-    }
-    __syncthreads();
-    for (int i0 = 0; i0 < p1 - p0; i0 += 4096) {
-      int xs[4], ds[4], rs[4];
-      unsigned long long wd[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {                  // 4 entries per thread, all loads in flight together
-        const int i = i0 + k * 1024 + tid;
-        xs[k] = -1;
-        if (i < p1 - p0) {
-          const int v = lst[i];
-          xs[k] = v >> 10;
-          ds[k] = d0 + (v & 1023);
-          const int b = kp_image(noff, B, ds[k]);
-          wd[k] = a.R[(int64_t)xs[k] * KP_W + ((ds[k] - noff[b]) >> 6)];
-          rs[k] = a.rowstart[xs[k]] + ebase[b];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (xs[k] >= 0) {
-          const int i = i0 + k * 1024 + tid;
-          const int dl = ds[k] - noff[kp_image(noff, B, ds[k])];
-          a.s_src[p0 + i] = xs[k];
-          a.s_dst[p0 + i] = ds[k];
-          a.s_orig[p0 + i] = rs[k] + pw[xs[k]][dl >> 6] + __popcll(wd[k] & ((1ull << (dl & 63)) - 1ull));
-        }
-      }
-    }
-  } else if (d0 + tid < d1) {                        // row by row, 8 sources at a time
-    const int d = d0 + tid;
-    const int b = kp_image(noff, B, d), ob = noff[b], nb = noff[b + 1] - ob, wpr = (nb + 63) >> 6;
-    const int dl = d - ob, dw = dl >> 6;
-    const unsigned long long below = (1ull << (dl & 63)) - 1ull;
-    const int eb = ebase[b];
-    int pos = cs[d];
-    unsigned long long rw[KP_W];
-#pragma unroll
-    for (int w = 0; w < KP_W; ++w) rw[w] = w < wpr ? a.R[(int64_t)d * KP_W + w] & M[b * KP_W + w] : 0ull;
-    for (;;) {
-      int xs[8], n = 0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {                  // the next (up to) 8 sources, from the bits alone
-        xs[k] = -1;                                  // (static indices only: rw stays in registers)
-        bool got = false;
-#pragma unroll
-        for (int w = 0; w < KP_W; ++w) {
-          if (!got && rw[w] != 0ull) {
-            xs[k] = ob + 64 * w + __builtin_ctzll(rw[w]);
-            rw[w] &= rw[w] - 1ull;
-            got = true;
-          }
-        }
-        if (got) n = k + 1;
-      }
-      if (n == 0) break;
-      unsigned long long wd[8];
-      int rs[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {                  // all their loads in flight together
-        wd[k] = xs[k] >= 0 ? a.R[(int64_t)xs[k] * KP_W + dw] : 0ull;
-        rs[k] = xs[k] >= 0 ? a.rowstart[xs[k]] : 0;
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        if (xs[k] >= 0) {
-          a.s_src[pos + k] = xs[k];
-          a.s_dst[pos + k] = d;
-          a.s_orig[pos + k] = eb + rs[k] + pw[xs[k]][dw] + __popcll(wd[k] & below);
-        }
-      }
-      pos += n;
-      if (n < 8) break;
-    }
-  }
-#if PEMP_KP_CLOCKS
-  __syncthreads();
-  KP_CLK(5);
-  if (tid == 0 && (t == 0 || t == T - 1))
-    printf("kp block %d,%d: start %lld init +%lld masks +%lld rows +%lld scan +%lld placed +%lld\n", t, blockIdx.y,
-           clk[0], clk[1] - clk[0], clk[2] - clk[0], clk[3] - clk[0], clk[4] - clk[0], clk[5] - clk[0]);
-#endif
-  if (t != T - 1 || blockIdx.y != 0) return;         // (block-uniform) one block closes seg and the split
-  if (tid == 0) {
-    int acc = 0;
-    for (int u = 0; u < T; ++u) { tst[u] = acc; acc += tot[u]; }
-    tst[T] = acc;
-    a.seg[(int64_t)T * N] = acc;
-    a.err[0] = (bad_sh ? 2 : 0) | (acc != a.E || ebase[B] != a.E ? 4 : 0);
-    a.err[1] = a.err[2] = a.err[3] = 0;
-  }
-  __syncthreads();
-  type_split(tst, tst[T], T, a.G, gt, a.wg_start);
-}
-
-static int launch_prepare(const pemp_mpn_desc* desc, const int64_t* edge_index, const int64_t* node_types, int64_t N,
-                          int64_t E, const MpnWs& ws, hipStream_t st) {
-  const int T = desc->num_types;
-  const int64_t tstride = desc->types_stride > 0 ? desc->types_stride : 1;   // node_types may be a strided view
-  const int64_t K = (int64_t)T * N;
-  ProfScope prof("mpn_prepare", st);
-  hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)std::min<int64_t>((K + 64 + 255) / 256, 1024)), dim3(256), 0,
-                     st, ws.err, K + 65);
-  PEMP_LAUNCH_CHECK();
-  if (E > 0) {
-    hipLaunchKernelGGL(mpn_count_kernel, dim3(grid1d(E, 256)), dim3(256), 0, st, edge_index, node_types, tstride, N, E, T,
-                       ws.cnt, ws.err);
-    PEMP_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(mpn_scan_kernel, dim3(1), dim3(1024), 0, st, ws.cnt, K, N, T, std::max(edge_cus(E), T), ws.seg,
-                     ws.wg_start);
-  PEMP_LAUNCH_CHECK();
-  if (E > 0) {
-    hipLaunchKernelGGL(mpn_scatter_kernel, dim3(grid1d(E, 256)), dim3(256), 0, st, edge_index, node_types, tstride, N, E, T,
-                       ws.seg, ws.cnt, ws.perm);
-    PEMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mpn_segsort_kernel, dim3((unsigned)((K + 15) / 16)), dim3(256), 0, st, edge_index, E, K, ws.seg,
-                       ws.perm, ws.s_src, ws.s_dst, ws.s_orig);
-    PEMP_LAUNCH_CHECK();
-  }
-  return PEMP_OK;
-}
-
-static int launch_prepare_sym(const pemp_mpn_desc* desc, const int64_t* edge_index, const int64_t* node_types,
-                              int64_t N, int64_t E, const MpnWs& ws, hipStream_t st) {
-  const int T = desc->num_types;
-  const int64_t tstride = desc->types_stride > 0 ? desc->types_stride : 1;
-  const int64_t K = (int64_t)T * N;
-  ProfScope prof("mpn_prepare_sym", st);
-  int2* rows = reinterpret_cast<int2*>(ws.sym);
-  int* flags = ws.sym + 2 * N;
-  unsigned* packed = reinterpret_cast<unsigned*>(ws.perm);
-  const unsigned g = (unsigned)((N + 3) / 4);                 // one wave per node
-  hipLaunchKernelGGL(sym_rows_kernel, dim3(g), dim3(256), 0, st, edge_index, node_types, tstride, N, E, T, ws.cnt, rows,
-                     packed, flags);
-  PEMP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sym_scan_kernel, dim3((unsigned)T), dim3(1024), 0, st, ws.cnt, N, T, std::max(edge_cus(E), T), ws.seg,
-                     ws.wg_start, flags, E, ws.err);
-  PEMP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sym_place_kernel, dim3(g), dim3(256), 0, st, N, T, ws.seg, rows, packed, ws.s_src, ws.s_dst,
-                     ws.s_orig, ws.err);
-  PEMP_LAUNCH_CHECK();
-  return PEMP_OK;
-}
-
 }  // namespace
 }  // namespace pemp
 
 using namespace pemp;
+
+#ifdef PEMP_STAMPS
+// diagnostic builds (the state sits beside EDGE_STAMP): which pass of every forward records its phase stamps, and where
+extern "C" int pemp_diag_stamps(void* buf, int pass) {
+  g_diag_stamps = static_cast<unsigned long long*>(buf);
+  g_diag_stamp_pass = pass;
+  return PEMP_OK;
+}
+#endif
 
 extern "C" size_t pemp_mpn_workspace_size(const pemp_mpn_desc* desc, int64_t N, int64_t E) {
   if (!desc || N < 0 || E < 0 || desc->num_types < 1) return 0;
@@ -3940,17 +2936,6 @@ extern "C" size_t pemp_mpn_workspace_size(const pemp_mpn_desc* desc, int64_t N, 
 // isolated forward 0.252 vs 0.242 ms, re-captured whenever N / E or the allocator's buffers change). The
 // capacity-mode forward, whose arguments repeat from step to step, is replayed from a graph:
 // pemp_mpn_forward_fully_cap.)
-#ifdef PEMP_STAMPS
-// diagnostic builds: the edge pass `g_diag_stamp_pass` of every forward records per-wave phase stamps
-static unsigned long long* g_diag_stamps = nullptr;
-static int g_diag_stamp_pass = 0;
-extern "C" int pemp_diag_stamps(void* buf, int pass) {
-  g_diag_stamps = static_cast<unsigned long long*>(buf);
-  g_diag_stamp_pass = pass;
-  return PEMP_OK;
-}
-#endif
-
 // ---- the inference forward: what a call is given (ForwardCall), its argument checks, everything derived from it
 // on the host (ForwardPlan), and the launches (Forward) ------------------------------------------------------------
 // where the type-major edge order of a forward comes from
@@ -4231,10 +3216,7 @@ struct Forward {
       case EdgeOrder::FULLY: {
         const FullyPrepArgs fa = fully_args();
         ProfScope prof("mpn_prepare_fully", st);
-        hipLaunchKernelGGL(fully_prepare_kernel, dim3((unsigned)p.grids.prep_gx, (unsigned)c.order.B), dim3(256), 0, st,
-                           fa);
-        PEMP_LAUNCH_CHECK();
-        return PEMP_OK;
+        return launch_prepare_fully(fa, p.grids.prep_gx, st);
       }
       case EdgeOrder::KNN: {
         KnnPrepArgs ka = *c.order.knn;
@@ -4242,10 +3224,7 @@ struct Forward {
         ka.seg = ws.seg; ka.wg_start = ws.wg_start; ka.s_src = ws.s_src; ka.s_dst = ws.s_dst; ka.s_orig = ws.s_orig;
         ka.err = ws.err;
         ProfScope prof("mpn_prepare_knn", st);
-        hipLaunchKernelGGL(knn_prepare_kernel, dim3((unsigned)p.T, (unsigned)((c.N + KP_CH - 1) / KP_CH)), dim3(1024),
-                           0, st, ka);
-        PEMP_LAUNCH_CHECK();
-        return PEMP_OK;
+        return launch_prepare_knn(ka, st);
       }
       case EdgeOrder::SYM: return launch_prepare_sym(c.desc, c.edge_index, c.node_types, c.N, c.E, ws, st);
       default: return launch_prepare(c.desc, c.edge_index, c.node_types, c.N, c.E, ws, st);
@@ -4455,15 +3434,11 @@ struct Forward {
     ea.ne = ne;
     ea.rec = rec;
     ea.write_next = !is_last;
-#ifdef PEMP_STAMPS
-    ea.stamps = it == g_diag_stamp_pass ? g_diag_stamps : nullptr;
-#endif
     if (it == 0 && p.fused_first) {   // embedding + pass 0 in one launch (it reads the first node table)
       ea.ea = c.edge_attr; ea.A = d.edge_attr_dim;
       ea.emb_img = c.w->edge_img + embed_image_offset(d, *c.w);
       ProfScope prof("edge_first", st);
-      hipLaunchKernelGGL((edge_step_kernel<PEMP_AGGR_ATTN, 0, 2, 1, STAGE_MID | STAGE_FIRST>), dim3(p.edge_grid),
-                         dim3(64 * EDGE_WAVES), 0, st, ea);
+      launch_edge_first(ea, it, p.edge_grid, st);
       PEMP_LAUNCH_CHECK();
       return PEMP_OK;
     }
@@ -4473,10 +3448,10 @@ struct Forward {
     // may repeat it between one event pair ("edge_step@R")
     for (int rep = prof_repeat(label); rep > 0; --rep) {
       switch (d.aggr) {
-        case PEMP_AGGR_ATTN: launch_edge_step<PEMP_AGGR_ATTN>(ea, record, pub, p.edge_grid, d.precision, p.upd_fused, stage, st); break;
-        case PEMP_AGGR_SUM: launch_edge_step<PEMP_AGGR_SUM>(ea, record, pub, p.edge_grid, d.precision, p.upd_fused, stage, st); break;
-        case PEMP_AGGR_MEAN: launch_edge_step<PEMP_AGGR_MEAN>(ea, record, pub, p.edge_grid, d.precision, p.upd_fused, stage, st); break;
-        default: launch_edge_step<PEMP_AGGR_MAX>(ea, record, pub, p.edge_grid, d.precision, false, stage, st); break;
+        case PEMP_AGGR_ATTN: launch_edge_step<PEMP_AGGR_ATTN>(ea, it, record, pub, p.edge_grid, d.precision, p.upd_fused, stage, st); break;
+        case PEMP_AGGR_SUM: launch_edge_step<PEMP_AGGR_SUM>(ea, it, record, pub, p.edge_grid, d.precision, p.upd_fused, stage, st); break;
+        case PEMP_AGGR_MEAN: launch_edge_step<PEMP_AGGR_MEAN>(ea, it, record, pub, p.edge_grid, d.precision, p.upd_fused, stage, st); break;
+        default: launch_edge_step<PEMP_AGGR_MAX>(ea, it, record, pub, p.edge_grid, d.precision, false, stage, st); break;
       }
       PEMP_LAUNCH_CHECK();
     }

@@ -1,4 +1,4 @@
-"""The type-major edge order every MPN forward starts from (csrc/mpn.hip: seg, wg_start, s_src, s_dst, s_orig),
+"""The type-major edge order every MPN forward starts from (csrc/mpn_order.hip: seg, wg_start, s_src, s_dst, s_orig),
 as tests/test_edge_order_cpu.py and tests/test_gpu_edge_order.py check it: a numpy reference of the order, heatmaps
 that make the graph constructor detect exactly a given number of nodes per image and type, and the read-back of
 the order from a model's workspace (pemp_mpn_order_layout). Helpers only, no tests."""
@@ -7,7 +7,7 @@ import ctypes
 import numpy as np
 import torch
 
-MAXT = 17                    # csrc/mpn.hip: wg_start holds MAXT + 2 words
+MAXT = 17                    # csrc/mpn_internal.h: wg_start holds MAXT + 2 words
 SDST_ID_MASK = 0xFFFFFF      # after a forward s_dst carries the passes' segment positions above the target id
 
 

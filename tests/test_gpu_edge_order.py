@@ -1,4 +1,4 @@
-"""The type-major edge order of the four prepares of csrc/mpn.hip (the sorting prepare, and the closed forms for the
+"""The type-major edge order of the four prepares of csrc/mpn_order.hip (the sorting prepare, and the closed forms for the
 constructor's fully graph, for symmetric sorted lists and for the knn build's bit rows), checked exactly -- integer
 arrays against the numpy reference of tests/edge_order.py -- at the sizes where each prepare takes another path or
 hands over to the next one. No tolerance anywhere in this file.

@@ -54,7 +54,7 @@ def test_knn_rows_layout_is_host_only():
 
 
 def test_edge_cu_reservation_is_a_bounded_share():
-    """The edge passes' CU reservation (mpn.hip edge_cus): small graphs keep every CU; large ones leave at most a
+    """The edge passes' CU reservation (mpn_internal.h edge_cus): small graphs keep every CU; large ones leave at most a
     quarter of the device free (a multiple of 8), whatever is asked, so a small device or a compute partition keeps
     at least 3/4 of its CUs for the forward (a fixed 64 would take most of such a device)."""
     L = _lib.load_cdll()

@@ -1,6 +1,6 @@
 """Stage-by-stage check of pemp_mpn_forward against a CPU recomputation (debug tool, GPU box).
 
-Reads the workspace slices (same carve order as csrc/mpn.hip mpn_carve) after a forward and
+Reads the workspace slices (same carve order as csrc/mpn_internal.h mpn_carve) after a forward and
 prints the max error of each stage: node/edge embedding, Q0, e' (sorted order), aggregation,
 node update, logits.
 """
